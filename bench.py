@@ -8,7 +8,11 @@ representation -> 50 x (select, dynamics, prediction, backup) -> sampling -> env
 + render + history + trajectory record; every RECORD_K steps the records are gathered
 (RCCL gather to rank 0 for N>1) into rank 0's pinned host buffer (the replay-buffer sink).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+       A plain run sets up, warms up, times the K steps and prints the line. --full adds what takes runs of its own:
+       the CPU baseline, the visit-count match against the CPU port and the f32 parity-path replay of the first timed
+       step. --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (same arguments = same
+       inputs, so two builds can be compared output for output).
        N>1 either under python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ... (WORLD_SIZE must
        equal N), or plain `python bench.py --gpus N`, which starts that torchrun as a child process itself.
 Prints ONE JSON line on rank 0.
@@ -44,10 +48,16 @@ def parse():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--cpu-envs", type=int, default=768,
                     help="bounded CPU sample (cpu_baseline + match rate): ~20 s of the CPU port on 16 host cores")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline, the visit-count match "
+                         "against the CPU port and the f32 parity-path replay (each can still be switched off)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline and the CPU-port match")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of HIP-graph replay")
     ap.add_argument("--no-parity", action="store_true",
-                    help="skip the f32 parity-path replay of the first timed step (full-batch visit-count match)")
+                    help="with --full: skip the f32 parity-path replay of the first timed step (full-batch "
+                         "visit-count match)")
     ap.add_argument("--learner-streams", type=int, default=2, choices=[1, 2],
                     help="learner: 2 = prediction nets on a side stream beside the dynamics chain")
     ap.add_argument("--tower-variant", type=int, default=0, help="tower kernel (mzba_tower_set_variant; 0 = by batch)")
@@ -68,6 +78,30 @@ def parse():
                     help="intra-op threads of the reference process whose temperature pow the sampling reproduces "
                          "(splits torch's pow into per-thread chunks from 3 x global envs >= 32768 on)")
     return ap.parse_args()
+
+
+DUMP_BUDGET = 48 << 20  # bytes of .npy payload per --dump-outputs directory (file headers come on top)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(path, arrays, rank=0):
+    """--dump-outputs: every array (tensor or ndarray) as float32 in path/<name>.npy (rank r > 0: <name>_rank<r>.npy).
+    Above DUMP_BUDGET in all, every array keeps the same fixed, seeded sample of its flattened elements (sorted
+    indices drawn from DUMP_SEED and the array's size only), so two runs with the same arguments keep the same ones."""
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for k, v in arrays.items():
+        if v is None:
+            continue
+        a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        host[k] = np.ascontiguousarray(a, dtype=np.float32)
+    total = sum(a.nbytes for a in host.values())
+    for k, a in host.items():
+        if total > DUMP_BUDGET:
+            keep = max(1, int(a.size * (DUMP_BUDGET / total) * 0.99))
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + (f"_rank{rank}" if rank else "") + ".npy"), a)
 
 
 def env_bytes(H, W):
@@ -137,8 +171,11 @@ def run_env(args, world, rank, local):
             if (e["envs"], e["H"], e["W"], e["hist"]) == (B, H, W, args.hist):
                 a_k = B * env_bytes(H, W) / (e["avg_ns"] * 1e-9) / 1e9
                 ktimed = {"avg_kernel_ms": e["avg_ns"] * 1e-6, "achieved": a_k, "frac": a_k / 8000.0, "source": e["source"]}
+    if args.dump_outputs:  # the env state and frame the last replayed step left
+        dump_outputs(args.dump_outputs, {"frame": env.current_frame().view(B, H * W), "reward": env.reward,
+                                         "done": env.done, "valid": env.valid}, rank)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         from oracle.env import BreakoutEnvOracle, convert_to_grayscale
         nb = min(B, 256)
         e = BreakoutEnvOracle({**cfg["environment"], "n_parallel": nb})
@@ -234,8 +271,11 @@ def run_learner(args, world, rank, local):
     fl = ln.flops_per_minibatch(B)
     peak = 157.3 if dt == "f32" else PEAK_BF16_TFLOPS
     achieved = fl / (kms * 1e-3) / 1e12
+    if args.dump_outputs:  # the last minibatch's losses and the parameters / running statistics it left
+        dump_outputs(args.dump_outputs, {"loss": loss, **{"param." + k: v.float() for k, v in ln.state_dict().items()}},
+                     rank)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         from oracle.learner import LearnerOracle
         from mzba.learner import MinibatchRing  # noqa: F401
         nb = 8
@@ -486,7 +526,7 @@ PEAK_F32_TFLOPS = 157.3  # MI355X dense f32 MFMA (MI355X_MICROARCH.md chip table
 
 
 def want_parity(args, rank, world):
-    return rank == 0 and world == 1 and not args.no_parity and args.dtype != "f32"
+    return rank == 0 and world == 1 and args.full and not args.no_parity and args.dtype != "f32"
 
 
 LOOP_STATE = ("paddle", "bx", "by", "dx", "dy", "done", "bricks", "cur_frame", "cur_src", "hist_frames", "hist_actions",
@@ -733,9 +773,9 @@ def main():
     if not args.no_graph:
         loop.capture()  # one acting step (~S x 65 launches) as a HIP graph, replayed per step
 
-    # ---- visit-count match + CPU baseline on a bounded sample (rank 0, N=1 only) -------
+    # ---- --full: visit-count match + CPU baseline on a bounded sample (rank 0, N=1 only) -------
     cpu_info, match, match_f32 = None, None, None
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu and not custom_geom
+    want_cpu = rank == 0 and world == 1 and args.full and not args.no_cpu and not custom_geom
     if want_cpu:
         nb = min(args.cpu_envs, B)
         cs = loop.cs
@@ -803,6 +843,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     value = world * B * args.steps / dt
+    if args.dump_outputs:  # the record row of the last timed step: what the step hands to the trajectory sink
+        dump_outputs(args.dump_outputs, {k: v[loop.t - 1] for k, v in loop.rec.items() if v is not None}, rank)
     runner.probe_collect()  # probe entries: (ms, convs in the launch), HIP events on the launch stream
     # per-conv average over the latent residual convs
     conv_ms = (float(sum(ms for ms, _ in probe) / sum(n for _, n in probe))) if probe else None

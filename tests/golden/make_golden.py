@@ -756,7 +756,9 @@ def make_learner(cfg):
                     out[f"s{step}/err_ref/grad/{k}"] = np.float64(np.abs(gr.astype(np.float64) - g64[k].numpy()).max())
             print("learner", tag, "step", step, "loss", float(res["loss"]), float(res["rl"]), float(res["vl"]),
                   float(res["pl"]))
-        np.savez_compressed(os.path.join(HERE, f"learner_{tag}.npz"), **out)
+        # above 1 MiB as one archive: stored in parts (learner_{tag}.NN.npz, oracle/fixtures.py)
+        from oracle.fixtures import save_npz_parts
+        save_npz_parts(HERE, f"learner_{tag}", {k: np.asarray(v) for k, v in out.items()})
 
 
 # --------------------------------------------------------------------------------------

@@ -128,3 +128,43 @@ def test_fp16_clock_record():
     r = bench.fp16_clock_note()
     assert r is not None and 0 < r["fp16_over_bf16_clock"] <= 1.0 and 0 < r["fp16_over_bf16_rate"] <= 1.0
     assert os.path.exists(os.path.join(ROOT, "profiles", "r06", "r6l", "mfma_clock_dtype.jsonl"))
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    """A plain run measures the headline only: the CPU baseline, the CPU-port match and the parity replay are behind
+    --full (off by default), where --no-cpu / --no-parity still switch their parts off."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (5, 2, False, None)
+    assert not bench.want_parity(a, 0, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out" and bench.want_parity(a, 0, 1)
+    assert not bench.want_parity(a, 0, 2) and not bench.want_parity(a, 1, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-parity"])
+    assert not bench.want_parity(bench.parse(), 0, 1)
+
+
+def test_dump_outputs_writes_float32_arrays_and_a_fixed_sample_above_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    arrays = {"counts": torch.arange(12, dtype=torch.int64).reshape(4, 3), "mask": np.array([1, 0, 1, 1], np.uint8),
+              "values": torch.linspace(-1, 1, 4), "absent": None}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert sorted(os.listdir(tmp_path / "a")) == ["counts.npy", "mask.npy", "values.npy"]
+    c = np.load(tmp_path / "a" / "counts.npy")
+    assert c.dtype == np.float32 and c.shape == (4, 3) and np.array_equal(c, np.arange(12).reshape(4, 3))
+    bench.dump_outputs(str(tmp_path / "a"), arrays, rank=1)  # other ranks beside rank 0's files
+    assert "counts_rank1.npy" in os.listdir(tmp_path / "a")
+    # above the budget: the same sorted sample of the flattened elements on every call, within the budget in all
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4000)
+    big = {"x": np.arange(3000, dtype=np.float64), "y": np.arange(1000, dtype=np.int32)}
+    bench.dump_outputs(str(tmp_path / "b"), big)
+    bench.dump_outputs(str(tmp_path / "c"), big)
+    tot = 0
+    for k, n in (("x", 3000), ("y", 1000)):
+        b, c = np.load(tmp_path / "b" / f"{k}.npy"), np.load(tmp_path / "c" / f"{k}.npy")
+        assert b.dtype == np.float32 and np.array_equal(b, c) and 0 < b.size < n
+        assert (np.diff(b) > 0).all() and b.max() < n  # arange input: the values are the sampled indices
+        tot += b.nbytes
+    assert tot <= 4000

@@ -214,7 +214,7 @@ def test_training_stage_runs_on_the_dropin_agent():
     """RLSystem._training_stage on this build's MuZeroAgent (train_torch.py:373-411): train_mode(), then the
     reference's own minibatch loop body — zero_grad, _k_step_rollout through create_hidden_state_root /
     evaluate_state / hidden_state_transition, loss_fn, loss.backward(), optimizer.step() — on the reference's two
-    training minibatches (tests/golden/learner_small.npz, narrow nets). The three nets run on the device learner's
+    training minibatches (tests/golden/learner_small.NN.npz, narrow nets). The three nets run on the device learner's
     HIP kernels behind torch.autograd. Against the reference: both steps' losses and logits within rtol 2e-4, the
     parameters after each Adam step within 2 lr (first-step updates are ~lr sign(g)), BN running statistics rtol
     1e-4. Against mzba.learner.Learner.train_minibatch on the same minibatch (same kernels, its fused loss kernel):
@@ -223,12 +223,13 @@ def test_training_stage_runs_on_the_dropin_agent():
     optimizer's state_dict is torch.optim.Adam's (train_torch.py:622, 652) and round-trips."""
     import os
     from conftest import GOLDEN
+    from oracle.fixtures import load_npz_parts
     from mzba.config import learner_model_cfg
     from mzba.learner import Learner, MinibatchRing
     from mzba.weights import init_state_dict
     from src.networks import MuZeroAgent
     from utils import ScalarTransforms
-    z = np.load(os.path.join(GOLDEN, "learner_small.npz"))
+    z = load_npz_parts(GOLDEN, "learner_small")
     mcfg, K, lr = learner_model_cfg(), int(z["K"]), float(z["lr"])
     mcfg = dict(mcfg, learning_rate=lr, device="cuda", dtype="f32")  # narrow nets: the f32 inference path
     start = init_state_dict(mcfg, int(z["seed"]))

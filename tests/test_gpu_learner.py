@@ -29,6 +29,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+from oracle.fixtures import load_npz_parts
 
 pytestmark = pytest.mark.gpu
 
@@ -114,7 +115,7 @@ def test_learner_small_matches_reference():
     from mzba.config import learner_model_cfg
     from mzba.learner import Learner, MinibatchRing
     from mzba.weights import init_state_dict
-    z = np.load(os.path.join(GOLDEN, "learner_small.npz"))
+    z = load_npz_parts(GOLDEN, "learner_small")
     mcfg, K, lr = learner_model_cfg(), int(z["K"]), float(z["lr"])
     start = init_state_dict(mcfg, int(z["seed"]))
     ln = Learner(mcfg, start, K=K)
@@ -146,7 +147,7 @@ def test_learner_full_matches_reference():
     from mzba.config import default_config
     from mzba.learner import Learner, MinibatchRing
     from mzba.weights import init_state_dict
-    z = np.load(os.path.join(GOLDEN, "learner_full.npz"))
+    z = load_npz_parts(GOLDEN, "learner_full")
     mcfg, K, lr = default_config()["model"], int(z["K"]), float(z["lr"])
     start = init_state_dict(mcfg, int(z["seed"]))
     ln = Learner(mcfg, start, K=K)
@@ -176,7 +177,7 @@ def test_learner_state_and_optimizer_roundtrip():
     from mzba.config import learner_model_cfg
     from mzba.learner import Learner, MinibatchRing
     from mzba.weights import init_state_dict
-    z = np.load(os.path.join(GOLDEN, "learner_small.npz"))
+    z = load_npz_parts(GOLDEN, "learner_small")
     mcfg = learner_model_cfg()
     sd0 = init_state_dict(mcfg, 3)
     ln = Learner(mcfg, sd0, K=int(z["K"]))
@@ -204,7 +205,7 @@ def test_checkpoint_carries_learner_optimizer_state(tmp_path):
     from mzba.config import learner_model_cfg
     from mzba.learner import Learner, MinibatchRing
     from mzba.weights import init_state_dict
-    z = np.load(os.path.join(GOLDEN, "learner_small.npz"))
+    z = load_npz_parts(GOLDEN, "learner_small")
     mcfg = learner_model_cfg()
     ln = Learner(mcfg, init_state_dict(mcfg, 3), K=int(z["K"]))
     ring = MinibatchRing(_mb(z, 1))

@@ -6,7 +6,8 @@
 # usage (repo root on the box): bash tools/gpu_run.sh TAG STEP [STEP ...]
 #   tests[:PYTEST_K]          pytest -m gpu [-k PYTEST_K]                    -> pytest.log
 #   smoke                     __graft_entry__.smoke()                          -> smoke.log
-#   bench:NAME[:ARGS]         python bench.py ARGS                            -> NAME.json (one JSON line)
+#   bench:NAME[:ARGS]         python bench.py ARGS                            -> NAME.json (one JSON line; ARGS with
+#                             --full for the cpu_baseline / visit_count_match / parity_path figures)
 #   prof:NAME[:ARGS]          rocprofv3 --kernel-trace --stats of bench.py     -> NAME_kernel_stats.csv
 #   pmc:B                     FETCH_SIZE / WRITE_SIZE passes (separate runs) of the tower kernel at B envs
 #                                                                              -> tower_hbm_traffic.json

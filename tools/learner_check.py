@@ -1,6 +1,6 @@
 """Learner parity diagnostics (prints every tensor, no early stop): the HIP learner's step-1
-gradients on tests/golden/learner_small.npz against the f64 oracle (with the reference's own
-f32 error beside them), on learner_full.npz against the reference's per-tensor |grad| sums, and
+gradients on tests/golden/learner_small.NN.npz against the f64 oracle (with the reference's own
+f32 error beside them), on learner_full.NN.npz against the reference's per-tensor |grad| sums, and
 the bf16 path's gradient cosines against the f32 path.
 usage: python tools/learner_check.py [small|full|bf16]...
 """
@@ -14,6 +14,7 @@ import torch  # noqa: E402
 from mzba.config import default_config, learner_model_cfg  # noqa: E402
 from mzba.learner import Learner, MinibatchRing  # noqa: E402
 from mzba.weights import init_state_dict  # noqa: E402
+from oracle.fixtures import load_npz_parts  # noqa: E402
 
 
 def mb_of(z, s):
@@ -37,7 +38,7 @@ def report(ln, mcfg, start, mb, K, tag):
 
 
 if "small" in which:
-    z = np.load(os.path.join(ROOT, "tests", "golden", "learner_small.npz"))
+    z = load_npz_parts(os.path.join(ROOT, "tests", "golden"), "learner_small")
     mcfg = learner_model_cfg()
     K = int(z["K"])
     start = init_state_dict(mcfg, int(z["seed"]))
@@ -53,7 +54,7 @@ if "small" in which:
         print("small", s, "loss", ln.train_minibatch(ring, ring.slots()).cpu().numpy(), float(z[f"s{s}/loss"]))
         report(ln, mcfg, start, mb_of(z, s), K, f"small{s}")
 if "full" in which:
-    z = np.load(os.path.join(ROOT, "tests", "golden", "learner_full.npz"))
+    z = load_npz_parts(os.path.join(ROOT, "tests", "golden"), "learner_full")
     mcfg = default_config()["model"]
     start = init_state_dict(mcfg, int(z["seed"]))
     ln = Learner(mcfg, start, K=int(z["K"]))
@@ -61,7 +62,7 @@ if "full" in which:
     print("full loss", ln.train_minibatch(ring, ring.slots()).cpu().numpy(), float(z["s1/loss"]))
     report(ln, mcfg, start, mb_of(z, 1), int(z["K"]), "full")
 if "bf16" in which:
-    z = np.load(os.path.join(ROOT, "tests", "golden", "learner_full.npz"))
+    z = load_npz_parts(os.path.join(ROOT, "tests", "golden"), "learner_full")
     mcfg = default_config()["model"]
     ring = MinibatchRing(mb_of(z, 1))
     out = {}
