@@ -90,6 +90,40 @@ class _Conv:
         self.fkind = self.dkind = "gen"  # kernels: "gen" (conv_igemm), "lat" (conv_lat), "band" (conv_band)
 
 
+class _Val:
+    """An activation or gradient between two launches: the row tensor `t` and what is still owed to it.
+
+    owed: the BatchNorm apply that fills `t`, not launched yet — forward (fwd) (BN input, stats, res, relu) for
+    mzba_bn_apply, backward (masked gradient, BN input, stats, coef) for mzba_bn_backward_apply. A consuming conv_lat
+    takes it into its staging prologue (take()); every other consumer launches it (ready()). While it is owed the
+    value is listed, in creation order, in `rec` (the learner's record of the stream it was created on).
+    masked: on a gradient that _dgrad(bn=...) masked for a BatchNorm — (that BN's output value, partials, chunks,
+    finalised coefficients or None), consumed by that BN's _bn_bwd."""
+    __slots__ = ("t", "owed", "fwd", "rec", "masked")
+
+    def __init__(self, t, owed=None, fwd=True, rec=None):
+        self.t, self.owed, self.fwd, self.rec, self.masked = t, owed, fwd, rec, None
+        if owed is not None:
+            rec[self] = None
+
+    def take(self):
+        """Hand the owed apply (or None) to the caller, who computes `t` in its own launch; the value is then plain."""
+        owed = self.owed
+        if owed is not None:
+            self.owed = None
+            del self.rec[self]
+        return owed
+
+    def ready(self):
+        """The tensor, after launching the owed apply (if any) on the current stream and dropping its operands."""
+        if self.owed is not None:
+            a, b, c, d = self.take()
+            L.call("mzba_bn_apply" if self.fwd else "mzba_bn_backward_apply", int(self.t.dtype == torch.bfloat16),
+                   L.ptr(a), L.ptr(b), L.ptr(c), int(d) if self.fwd else L.ptr(d), L.ptr(self.t), *self.t.shape,
+                   L.stream())
+        return self.t
+
+
 class Learner:
     """Device learner for one `MuZeroAgent` (mu_zero) + its Adam optimizer.
 
@@ -139,10 +173,8 @@ class Learner:
             fuse_fin = os.environ.get("MZBA_BN_FIN", "0") != "0"
         self.fuse_fin = bool(fuse_fin)
         self._ctr, self._ctr_i = None, 0
-        self._gpart = {}
-        self._lazy = {}  # BN outputs whose apply rides on the consuming conv_lat (id(y) -> (y, t, stats, res, relu))
-        self._lazyb = {}  # BN input gradients likewise (id(dt) -> (dt, g, t, stats, coef))
-        self._pending = None
+        self._owed = {}  # the values (_Val) that still owe their BN apply, in creation order (an ordered set)
+        self._pending = None  # deferred latent weight gradients: conv -> [(x, dY)] in backward order
         self._graph = None        # captured minibatch (capture()), replayed by train_minibatch
         self._capturing = False
         if dtype not in ("f32", "bf16"):
@@ -352,17 +384,19 @@ class Learner:
             self._side_stream = torch.cuda.Stream(self.device)
         side = self._side_stream
         side.wait_stream(main)
-        lz, lzb = set(self._lazy), set(self._lazyb)
+        outer, self._owed = self._owed, {}  # the block's own record
         self._tag = "@side"
         try:
             with torch.cuda.stream(side):
                 yield
-                for k in [k for k in self._lazy if k not in lz]:
-                    self._materialize(self._lazy[k][0])
-                for k in [k for k in self._lazyb if k not in lzb]:
-                    self._materialize_b(self._lazyb[k][0])
+                self._settle()
         finally:
-            self._tag = ""
+            self._tag, self._owed = "", outer
+
+    def _settle(self):
+        """Launch every apply still owed on this stream's record, in creation order."""
+        for v in list(self._owed):
+            v.ready()
 
     def _join(self, *shared):
         """Main stream waits for the side stream; tensors crossing streams are recorded on both."""
@@ -448,10 +482,10 @@ class Learner:
         L.call("mzba_conv_lat_bn_chunks", B, H, W, cin, cout, ks, ctypes.byref(nc), ctypes.byref(rpc))
         part = torch.empty(nc.value * cout * 2, dtype=torch.float32, device=self.device)
         ps, pr, prelu, po, pc = pro if pro is not None else (None, None, 0, None, None)
+        args = (L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(res), L.ptr(out), B, H, W, cin, cout, ks, mode, L.ptr(part),
+                L.ptr(y), L.ptr(t), L.ptr(stats), L.ptr(ps), L.ptr(pr), int(prelu), L.ptr(po), L.ptr(pc))
         if fin is None:
-            L.call("mzba_conv_lat_bn", L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(res), L.ptr(out), B, H, W, cin, cout, ks,
-                   mode, L.ptr(part), L.ptr(y), L.ptr(t), L.ptr(stats), L.ptr(ps), L.ptr(pr), int(prelu), L.ptr(po),
-                   L.ptr(pc), L.stream())
+            L.call("mzba_conv_lat_bn", *args, L.stream())
             return part, nc.value, rpc.value
         ctr = self._ctr_take(cout // 128)
         if mode == 1:
@@ -460,33 +494,13 @@ class Learner:
         else:
             dg, db, coef = fin
             fargs = (None, None, L.ptr(stats), None, None, L.ptr(dg), L.ptr(db), L.ptr(coef))
-        L.call("mzba_conv_lat_bn_fin", L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(res), L.ptr(out), B, H, W, cin, cout, ks,
-               mode, L.ptr(part), L.ptr(y), L.ptr(t), L.ptr(stats), L.ptr(ps), L.ptr(pr), int(prelu), L.ptr(po),
-               L.ptr(pc), L.ptr(ctr), BN_EPS, BN_MOMENTUM, *fargs, L.stream())
+        L.call("mzba_conv_lat_bn_fin", *args, L.ptr(ctr), BN_EPS, BN_MOMENTUM, *fargs, L.stream())
         return part, nc.value, rpc.value
 
-    def _materialize(self, y):
-        """Run the deferred apply of BN output y (when no conv_lat consumed it)."""
-        e = self._lazy.pop(id(y), None)
-        if e is not None and e[0] is y:
-            _, t, stats, res, relu = e
-            L.call("mzba_bn_apply", self.dt, L.ptr(t), L.ptr(stats), L.ptr(res), int(relu), L.ptr(y), t.shape[0],
-                   t.shape[1], L.stream())
-        return y
-
-    def _materialize_b(self, dt):
-        """Run the deferred apply of BN input gradient dt (when no conv_lat consumed it)."""
-        e = self._lazyb.pop(id(dt), None)
-        if e is not None and e[0] is dt:
-            _, g, t, stats, coef = e
-            L.call("mzba_bn_backward_apply", self.dt, L.ptr(g), L.ptr(t), L.ptr(stats), L.ptr(coef), L.ptr(dt),
-                   t.shape[0], t.shape[1], L.stream())
-        return dt
-
     def _conv(self, c, x, B, H, W, bn=False):
-        """Forward conv; bn: a BatchNorm consumes the output (its statistics may ride on the conv).
-        A deferred BN output x is applied while staging when both ride on conv_lat.
-        Returns (output, fused partials or None)."""
+        """Forward conv of value x; bn: a BatchNorm consumes the output (its statistics may ride on the conv).
+        A BN apply x still owes runs while staging when both ride on conv_lat.
+        Returns (output tensor, fused partials or None)."""
         t = self._act(B * H * W, c.cout)
         if bn and self._fusable(c.fkind, c.cout):
             fin = fst = None
@@ -494,82 +508,77 @@ class Learner:
                 fst = torch.empty(4, c.cout, dtype=torch.float32, device=self.device)
                 rm, rv = self.run[c.bn_key]
                 fin = (fst, c.gamma, c.beta, rm, rv)
-            e = self._lazy.pop(id(x), None)
-            if e is not None and e[0] is x:  # x = [relu](t' * alpha + beta' [+ res]) computed in the staging
-                _, tp, st, res, relu = e
-                return t, self._lat_bn(tp, c.wf, c.b, None, t, B, H, W, c.cin_p, c.cout, c.ks, 1,
-                                       pro=(st, res, relu, x, None), fin=fin) + (fst,)
-            return t, self._lat_bn(x, c.wf, c.b, None, t, B, H, W, c.cin_p, c.cout, c.ks, 1, fin=fin) + (fst,)
-        self._materialize(x)
-        self._run_conv(c.fkind, x, c.cin_p, c.w if self.dt == 0 else c.wf, c.b, None, t, B, H, W, c.cout, c.ks)
+            owed, pro, src = x.take(), None, x.t
+            if owed is not None:  # x = [relu](t' * alpha + beta' [+ res]) computed in the staging
+                src, st, res, relu = owed
+                pro = (st, res, relu, x.t, None)
+            part = self._lat_bn(src, c.wf, c.b, None, t, B, H, W, c.cin_p, c.cout, c.ks, 1, pro=pro, fin=fin)
+            return t, part + (fst,)
+        self._run_conv(c.fkind, x.ready(), c.cin_p, c.w if self.dt == 0 else c.wf, c.b, None, t, B, H, W, c.cout, c.ks)
         return t, None
 
     def _bn(self, c, t, res=None, relu=True, fpart=None):
+        """Train-mode BatchNorm of conv output t (+ value res, ReLU) -> (output value, stats)."""
         M = t.shape[0]
         stats = torch.empty(4, c.cout, dtype=torch.float32, device=self.device)
         rm, rv = self.run[c.bn_key]
-        if fpart is not None:  # statistics from the producing conv; the apply is deferred to the consumer
+        if fpart is not None:  # statistics from the producing conv; the apply is left to the consumer
             part, nc, rpc, fst = fpart
             if fst is not None:  # finalised in the producing launch (mzba_conv_lat_bn_fin)
                 stats = fst
             else:
                 L.call("mzba_bn_stats_final", L.ptr(part), nc, rpc, M, c.cout, BN_EPS, BN_MOMENTUM, L.ptr(c.gamma),
                        L.ptr(c.beta), L.ptr(stats), L.ptr(rm), L.ptr(rv), L.stream())
-            self.nbt[c.bn_key] += 1
-            y = self._act(M, c.cout)
-            self._lazy[id(y)] = (y, t, stats, res, relu)
-            return y, stats
         else:
             ws = self._scratch("bn", ((M + 63) // 64) * c.cout * 8 + 12 * c.cout)
             L.call("mzba_bn_stats", self.dt, L.ptr(t), M, c.cout, BN_EPS, BN_MOMENTUM, L.ptr(c.gamma), L.ptr(c.beta),
                    L.ptr(stats), L.ptr(rm), L.ptr(rv), L.ptr(ws), ws.numel(), L.stream())
         self.nbt[c.bn_key] += 1
-        y = self._act(M, c.cout)
-        L.call("mzba_bn_apply", self.dt, L.ptr(t), L.ptr(stats), L.ptr(res), int(relu), L.ptr(y), M, c.cout,
-               L.stream())
+        y = _Val(self._act(M, c.cout), (t, stats, None if res is None else res.ready(), relu), True, self._owed)
+        if fpart is None:
+            y.ready()
         return y, stats
 
     def _bn_bwd(self, c, dy, y, t, stats):
+        """Input gradient of BatchNorm c (output value y, input t) from the gradient value dy of y. A dy that _dgrad
+        masked for y brings the partial sums (the apply is then left to the consumer); one masked for another
+        BatchNorm is a wiring error (with fuse_fin its launch has already added to that BN's dgamma / dbeta)."""
+        m = dy.masked
+        if m is not None and m[0] is not y:
+            raise RuntimeError(f"Learner: gradient masked for another BatchNorm reached the backward of {c.bn_key}")
         M = t.shape[0]
         dt = self._act(M, c.cout)
-        e = self._gpart.pop(id(dy), None)
-        if e is not None and e[0] is dy and e[1] is y and self.dt == 1:
-            # dy came masked with partials from its producing conv; the apply rides on the consumer
-            coef = e[4]  # finalised in the producing launch (mzba_conv_lat_bn_fin), else here
+        if m is not None:
+            _, part, nc, coef = m  # coef finalised in the producing launch (mzba_conv_lat_bn_fin), else here
             if coef is None:
                 coef = torch.empty(3 * c.cout, dtype=torch.float32, device=self.device)
-                L.call("mzba_bn_backward_coef", L.ptr(e[2]), e[3], M, c.cout, L.ptr(stats), L.ptr(c.dgamma),
+                L.call("mzba_bn_backward_coef", L.ptr(part), nc, M, c.cout, L.ptr(stats), L.ptr(c.dgamma),
                        L.ptr(c.dbeta), L.ptr(coef), L.stream())
-            self._lazyb[id(dt)] = (dt, dy, t, stats, coef)
-            return dt
-        if e is not None and e[0] is dy and e[1] is y:  # dy came masked, partials from its producing conv
-            ws = self._scratch("bnf", 12 * c.cout)
-            L.call("mzba_bn_backward_final", self.dt, L.ptr(dy), L.ptr(t), L.ptr(stats), L.ptr(e[2]), e[3], M, c.cout,
-                   L.ptr(c.dgamma), L.ptr(c.dbeta), L.ptr(dt), L.ptr(ws), ws.numel(), L.stream())
-            return dt
+            dy.masked = None
+            return _Val(dt, (dy.t, t, stats, coef), False, self._owed)
         ws = self._scratch("bn", ((M + 63) // 64) * c.cout * 8 + 12 * c.cout)
-        L.call("mzba_bn_backward", self.dt, L.ptr(dy), L.ptr(y), L.ptr(t), L.ptr(stats), M, c.cout, L.ptr(c.dgamma),
-               L.ptr(c.dbeta), L.ptr(dt), L.ptr(ws), ws.numel(), L.stream())
-        return dt
+        L.call("mzba_bn_backward", self.dt, L.ptr(dy.ready()), L.ptr(y.ready()), L.ptr(t), L.ptr(stats), M, c.cout,
+               L.ptr(c.dgamma), L.ptr(c.dbeta), L.ptr(dt), L.ptr(ws), ws.numel(), L.stream())
+        return _Val(dt)
 
     def _wgrad(self, c, x, dy, B, H, W):
-        self._materialize_b(dy)
+        x, dy = x.ready(), dy.ready()
         if self._pending is not None and (H, W) == self.lat:
             # latent convs run K times per minibatch with the same weights: their weight gradients
             # are reduced in one contraction over the K (x, dY) pairs after the unrolled backward
-            self._pending.setdefault(id(c), (c, []))[1].append((x, dy))
+            self._pending.setdefault(c, []).append((x, dy))
             return
         nb = L.lib().mzba_conv_wgrad_ws_bytes(B, H, W, c.cin_p, c.cout, c.ks)
         ws = self._scratch("wg", nb)
         L.call("mzba_conv_wgrad", self.dt, L.ptr(x), L.ptr(dy), B, H, W, c.cin_p, c.cout, c.ks, L.ptr(c.dw),
                L.ptr(c.db), L.ptr(ws), ws.numel(), L.stream())
 
-    def _flush_wgrad(self, B, convs=None):
-        """mzba_conv_wgrad_segs over every deferred latent conv (or those in `convs`; segments in
+    def _flush_wgrad(self, B):
+        """mzba_conv_wgrad_segs over every deferred latent conv (convs in first-deferred order, segments in
         backward order, so per-segment kernels accumulate exactly as the immediate calls would)."""
         H, W = self.lat
-        keys = [k for k in self._pending if convs is None or any(k == id(c) for c in convs)]
-        for c, segs in [self._pending.pop(k) for k in keys]:
+        pending, self._pending = self._pending, {}
+        for c, segs in pending.items():
             for i in range(0, len(segs), 8):
                 part = segs[i:i + 8]
                 n = len(part)
@@ -584,52 +593,50 @@ class Learner:
                         t.record_stream(torch.cuda.current_stream(self.device))
 
     def _dgrad(self, c, dy, B, H, W, acc=None, bn=None):
-        """Input gradient of conv c (first cin_used channels); added into `acc` when given.
-        bn = (BN conv, its output y, its input t, its stats): the BatchNorm whose output gradient this
-        is — its ReLU mask and partial sums then ride on this conv (consumed by _bn_bwd)."""
+        """Input gradient value of conv c (first cin_used channels) from the gradient value dy; added into the
+        value `acc` when given. bn = (BN conv, its output value y, its input t, its stats): the BatchNorm whose
+        output gradient this is — its ReLU mask and partial sums then ride on this conv (consumed by _bn_bwd)."""
         cu = min(c.cin, self.c1) if c is self.dyn_block else c.cin_p
-        out = acc if acc is not None else self._act(B * H * W, cu)
-        lb = self._lazyb.get(id(dy))
-        pro = None
-        if lb is not None and lb[0] is dy and self._fusable(c.dkind, cu):  # dy computed while staging
-            self._lazyb.pop(id(dy))
-            _, gp, tp, stp, coef = lb
-            pro, src = (stp, tp, 0, dy, coef), gp
+        out = acc if acc is not None else _Val(self._act(B * H * W, cu))
+        acc = None if acc is None else acc.t
+        fused = self._fusable(c.dkind, cu)
+        owed, pro = dy.take() if fused else None, None
+        if owed is not None:  # dy computed while staging
+            src, tp, stp, coef = owed
+            pro = (stp, tp, 0, dy.t, coef)
         else:
-            self._materialize_b(dy)
-            src = dy
-        if (bn is not None or pro is not None) and self._fusable(c.dkind, cu):
-            if bn is not None:
-                bc, y, t, st = bn
-                fin = coef = None
-                if self.fuse_fin:  # the BN's backward finaliser rides on this launch
-                    coef = torch.empty(3 * cu, dtype=torch.float32, device=self.device)
-                    fin = (bc.dgamma, bc.dbeta, coef)
-                part, nc, _ = self._lat_bn(src, c.wt, self._zero, acc, out, B, H, W, c.cout, cu, c.ks, 2, y, t, st,
-                                           pro=pro, fin=fin)
-                self._gpart[id(out)] = (out, y, part, nc, coef)
-            else:
-                self._lat_bn(src, c.wt, self._zero, acc, out, B, H, W, c.cout, cu, c.ks, 0, pro=pro)
-            return out
-        self._run_conv(c.dkind, dy, c.cout, c.wt, self._zero, acc, out, B, H, W, cu, c.ks)
+            src = dy.ready()
+        if fused and bn is not None:
+            bc, y, t, st = bn
+            fin = coef = None
+            if self.fuse_fin:  # the BN's backward finaliser rides on this launch
+                coef = torch.empty(3 * cu, dtype=torch.float32, device=self.device)
+                fin = (bc.dgamma, bc.dbeta, coef)
+            part, nc, _ = self._lat_bn(src, c.wt, self._zero, acc, out.t, B, H, W, c.cout, cu, c.ks, 2, y.ready(), t,
+                                       st, pro=pro, fin=fin)
+            out.masked = (y, part, nc, coef)
+        elif pro is not None:
+            self._lat_bn(src, c.wt, self._zero, acc, out.t, B, H, W, c.cout, cu, c.ks, 0, pro=pro)
+        else:
+            self._run_conv(c.dkind, src, c.cout, c.wt, self._zero, acc, out.t, B, H, W, cu, c.ks)
         return out
 
     def _linear(self, key, x, B, cin, O, out):
-        self._materialize(x)
         K = self.lat[0] * self.lat[1] * cin
-        L.call("mzba_linear_forward", self.dt, L.ptr(x), L.ptr(self._view(key + ".weight")),
+        L.call("mzba_linear_forward", self.dt, L.ptr(x.ready()), L.ptr(self._view(key + ".weight")),
                L.ptr(self._view(key + ".bias")), L.ptr(out), B, K, O, L.stream())
 
     def _linear_bwd(self, key, x, dy, B, cin, O):
+        """Input gradient value of a head's Linear on the value x from the logit gradient tensor dy."""
         K = self.lat[0] * self.lat[1] * cin
         dx = self._act(B * self.lat[0] * self.lat[1], cin)
         ws = self._scratch("lin", L.lib().mzba_linear_ws_bytes(B, K, O))
-        L.call("mzba_linear_backward", self.dt, L.ptr(x), L.ptr(self._view(key + ".weight")), L.ptr(dy), L.ptr(dx), 0,
-               L.ptr(self._gview(key + ".weight")), L.ptr(self._gview(key + ".bias")), B, K, O, L.ptr(ws), ws.numel(),
-               L.stream())
-        return dx
+        L.call("mzba_linear_backward", self.dt, L.ptr(x.ready()), L.ptr(self._view(key + ".weight")), L.ptr(dy),
+               L.ptr(dx), 0, L.ptr(self._gview(key + ".weight")), L.ptr(self._gview(key + ".bias")), B, K, O, L.ptr(ws),
+               ws.numel(), L.stream())
+        return _Val(dx)
 
-    # -- blocks: forward returns (out, saved); backward takes the output gradient ------------------------
+    # -- blocks on values (_Val): forward returns (out, saved); backward takes the output gradient ---------
     def _res_fwd(self, r, x, B, H, W):
         c1, c2 = r
         t1, p1 = self._conv(c1, x, B, H, W, bn=True)
@@ -644,26 +651,21 @@ class Learner:
         x, t1, a1, s1, t2, s2, out = sv
         return (r[1], out, t2, s2)
 
-    def _res_bwd(self, r, sv, g, gx, B, H, W, nxt=None):
-        """g: gradient of the block output (overwritten with the ReLU-masked gradient);
-        gx: existing gradient of the block input or None. Returns the input gradient."""
+    def _res_bwd(self, r, sv, g, B, H, W, nxt=None):
+        """g: gradient of the block output (overwritten with the ReLU-masked gradient, then the input gradient
+        is added into it: the skip path). nxt: the BN that consumes the result (_dgrad's bn=). Returns g."""
         c1, c2 = r
         x, t1, a1, s1, t2, s2, out = sv
         dt2 = self._bn_bwd(c2, g, out, t2, s2)           # g <- g * [out > 0]
-        # input gradient first: it computes a deferred dt while staging, then the weight gradient reads it
+        # input gradient first: it computes an owed dt while staging, then the weight gradient reads it
         da1 = self._dgrad(c2, dt2, B, H, W, bn=(c1, a1, t1, s1))
         self._wgrad(c2, a1, dt2, B, H, W)
         del dt2
         dt1 = self._bn_bwd(c1, da1, a1, t1, s1)
         del da1
-        if gx is None:                                     # skip path: the masked g itself
-            out = self._dgrad(c1, dt1, B, H, W, acc=g, bn=nxt)
-            self._wgrad(c1, x, dt1, B, H, W)
-            return out
-        self._dgrad(c1, dt1, B, H, W, acc=gx)
+        self._dgrad(c1, dt1, B, H, W, acc=g, bn=nxt)
         self._wgrad(c1, x, dt1, B, H, W)
-        L.call("mzba_axpy", self.dt, L.ptr(gx), L.ptr(g), gx.numel(), L.stream())
-        return gx
+        return g
 
     def _block_fwd(self, c, x, B, H, W):  # ConvBlock: conv -> BN -> ReLU
         t, p = self._conv(c, x, B, H, W, bn=True)
@@ -678,14 +680,14 @@ class Learner:
         return out
 
     def _scale_fwd(self, h, B):
-        self._materialize(h)
+        h = h.ready()
         hw, C = h.shape[0] // B, h.shape[1]
         out = self._act(h.shape[0], C)
         mm = torch.empty(B, 2, dtype=torch.float32, device=self.device)
         idx = torch.empty(B, 2, dtype=torch.int32, device=self.device)
         L.call("mzba_scale_forward", self.dt, L.ptr(h), L.ptr(out), L.ptr(mm), L.ptr(idx), B, hw, C, L.stream())
         self._scale_idx.append((idx, hw, C))
-        return out, (h, mm, idx)
+        return _Val(out), (h, mm, idx)
 
     def scale_indices(self):
         """(argmin, argmax) of every _scale_state of the last minibatch (representation, then
@@ -698,10 +700,113 @@ class Learner:
 
     def _scale_bwd(self, sv, dy, B, acc=None):
         h, mm, idx = sv
-        out = acc if acc is not None else self._act(*h.shape)
-        L.call("mzba_scale_backward", self.dt, L.ptr(dy), L.ptr(h), L.ptr(mm), L.ptr(idx), L.ptr(out), B,
+        out = acc if acc is not None else _Val(self._act(*h.shape))
+        L.call("mzba_scale_backward", self.dt, L.ptr(dy.ready()), L.ptr(h), L.ptr(mm), L.ptr(idx), L.ptr(out.t), B,
                h.shape[0] // B * h.shape[1], int(acc is not None), L.stream())
         return out
+
+    # -- the three nets: each forward and backward once, for the fused minibatch and the per-call mode alike;
+    # values in and out, logits into the caller's tensors, each forward returns what its backward needs ------
+    def _rep_fwd(self, x, B):
+        """RepresentationNetwork + _scale_state on the input rows x -> (scaled root latent, saved)."""
+        s = L.stream()
+        tape, h, hh, ww = [], x, 16, 20
+        for kind, mod in self.rep:
+            if kind == "conv":
+                y, _ = self._conv(mod, h, B, hh, ww)
+                tape.append(("conv", mod, (h, hh, ww)))
+                h = _Val(y)
+            elif kind == "res":
+                h, sv = self._res_fwd(mod, h, B, hh, ww)
+                tape.append(("res", mod, (sv, hh, ww)))
+            else:
+                C = h.t.shape[1]
+                y = self._act(B * (hh // 2) * (ww // 2), C)
+                L.call("mzba_avgpool2", self.dt, L.ptr(h.ready()), L.ptr(y), B, hh, ww, C, s)
+                tape.append(("pool", None, (hh, ww, C)))
+                h, hh, ww = _Val(y), hh // 2, ww // 2
+        h, sc = self._scale_fwd(h, B)
+        return h, (tape, sc)
+
+    def _rep_bwd(self, saved, gh, B):
+        """Weight gradients of the representation from d(scaled root latent) gh: scale -> [pool | res | conv] reversed"""
+        tape, sc = saved
+        s = L.stream()
+        gx = self._scale_bwd(sc, gh, B)
+        for ti in reversed(range(len(tape))):
+            kind, mod, sv = tape[ti]
+            prev = tape[ti - 1] if ti > 0 else None
+            nxt = self._res_in_bn(prev[1], prev[2][0]) if prev is not None and prev[0] == "res" else None
+            if kind == "pool":
+                hh, ww, C = sv
+                dx = self._act(B * hh * ww, C)
+                L.call("mzba_avgpool2_backward", self.dt, L.ptr(gx.ready()), L.ptr(dx), B, hh, ww, C, s)
+                gx = _Val(dx)
+            elif kind == "res":
+                svr, hh, ww = sv
+                gx = self._res_bwd(mod, svr, gx, B, hh, ww, nxt=nxt)
+            else:
+                xin, hh, ww = sv
+                self._wgrad(mod, xin, gx, B, hh, ww)
+                gx = self._dgrad(mod, gx, B, hh, ww) if mod is not self.rep[0][1] else None
+
+    def _pred_fwd(self, h, B, lp, lv):
+        """PredictionNetwork on the latent h: policy logits into lp [B][na], value logits into lv [B][ns] -> saved."""
+        hl, wl = self.lat
+        xp, psv = h, []
+        for r in self.pred_res:
+            xp, sv = self._res_fwd(r, xp, B, hl, wl)
+            psv.append(sv)
+        yp, spol = self._block_fwd(self.pred_pconv, xp, B, hl, wl)
+        self._linear(self.pred_plin[0], yp, B, self.pred_plin[1], self.na, lp)
+        yv, sval = self._block_fwd(self.pred_vconv, xp, B, hl, wl)
+        self._linear(self.pred_vlin[0], yv, B, self.pred_vlin[1], self.ns, lv)
+        return dict(psv=psv, spol=spol, sval=sval, yp=yp, yv=yv)
+
+    def _pred_bwd(self, u, dlp, dlv, B):
+        """heads -> res blocks -> d h (applied) from the policy / value logit gradients (contiguous [B][n] f32)."""
+        hl, wl = self.lat
+        dyv = self._linear_bwd(self.pred_vlin[0], u["yv"], dlv, B, self.pred_vlin[1], self.ns)
+        gp = self._block_bwd(self.pred_vconv, u["sval"], dyv, B, hl, wl)
+        dyp = self._linear_bwd(self.pred_plin[0], u["yp"], dlp, B, self.pred_plin[1], self.na)
+        pcons = [self._res_in_bn(r, sv) for r, sv in zip(self.pred_res, u["psv"])]
+        self._block_bwd(self.pred_pconv, u["spol"], dyp, B, hl, wl, acc=gp, nxt=pcons[-1] if pcons else None)
+        del dyv, dyp
+        for i in reversed(range(len(self.pred_res))):
+            gp = self._res_bwd(self.pred_res[i], u["psv"][i], gp, B, hl, wl, nxt=pcons[i - 1] if i > 0 else None)
+        gp.ready()
+        return gp
+
+    def _dyn_fwd(self, xin, B, lr):
+        """DynamicsNetwork + _scale_state on the built input xin (latent, action planes): reward logits into lr
+        [B][ns] -> (next scaled latent, saved)."""
+        hl, wl = self.lat
+        xd, sblk = self._block_fwd(self.dyn_block, xin, B, hl, wl)
+        dsv = []
+        for r in self.dyn_res:
+            xd, sv = self._res_fwd(r, xd, B, hl, wl)
+            dsv.append(sv)
+        yr, srew = self._block_fwd(self.dyn_rconv, xd, B, hl, wl)
+        self._linear(self.dyn_rlin[0], yr, B, self.dyn_rlin[1], self.ns, lr)
+        h_next, ssc = self._scale_fwd(xd, B)
+        return h_next, dict(sblk=sblk, dsv=dsv, yr=yr, srew=srew, ssc=ssc)
+
+    def _dyn_bwd(self, u, gh_next, dlr, B):
+        """scale -> reward head -> res blocks -> conv block -> d h (the first c1 input channels, applied) from
+        d(next scaled latent) (or None) and the reward logit gradient (contiguous [B][ns] f32)."""
+        hl, wl = self.lat
+        gx = self._scale_bwd(u["ssc"], gh_next, B) if gh_next is not None else None
+        dyr = self._linear_bwd(self.dyn_rlin[0], u["yr"], dlr, B, self.dyn_rlin[1], self.ns)
+        xb, tb, sb, yb = u["sblk"]
+        dcons = [(self.dyn_block, yb, tb, sb)] + [self._res_in_bn(r, sv) for r, sv in zip(self.dyn_res, u["dsv"])]
+        gx = self._block_bwd(self.dyn_rconv, u["srew"], dyr, B, hl, wl, acc=gx, nxt=dcons[-1])
+        del dyr
+        for i in reversed(range(len(self.dyn_res))):
+            gx = self._res_bwd(self.dyn_res[i], u["dsv"][i], gx, B, hl, wl, nxt=dcons[i])
+        gh = self._block_bwd(self.dyn_block, u["sblk"], gx, B, hl, wl)
+        del gx
+        gh.ready()
+        return gh
 
     # -- one minibatch ------------------------------------------------------------------------------
     def train_minibatch(self, ring, slots):
@@ -775,9 +880,7 @@ class Learner:
         self.G.zero_()
         self._scale_idx = []
         self._pending = {} if self.defer_wgrad else None
-        self._gpart = {}
-        self._lazy = {}
-        self._lazyb = {}
+        self._owed = {}
         self._ctr_i = 0
         self._prepare_packs()
         # ---- forward (_k_step_rollout)
@@ -785,61 +888,26 @@ class Learner:
         x = self._act(B * H * W, cin_p)
         L.call("mzba_learner_input", self.dt, L.ptr(g["states"]), L.ptr(g["past_actions"]), L.ptr(slots),
                L.ptr(self._lut), L.ptr(x), B, Lh, H * W, cin_p, s)
-        tape, h, hh, ww = [], x, H, W
-        for kind, mod in self.rep:
-            if kind == "conv":
-                y, _ = self._conv(mod, h, B, hh, ww)
-                tape.append(("conv", mod, (h, hh, ww)))
-                h = y
-            elif kind == "res":
-                h, sv = self._res_fwd(mod, h, B, hh, ww)
-                tape.append(("res", mod, (sv, hh, ww)))
-            else:
-                y = self._act(B * (hh // 2) * (ww // 2), h.shape[1])
-                self._materialize(h)
-                L.call("mzba_avgpool2", self.dt, L.ptr(h), L.ptr(y), B, hh, ww, h.shape[1], s)
-                tape.append(("pool", None, (hh, ww, h.shape[1])))
-                h, hh, ww = y, hh // 2, ww // 2
-        h, rep_scale = self._scale_fwd(h, B)
+        h, rep_saved = self._rep_fwd(_Val(x), B)
         lr_all = torch.empty(K, B, self.ns, device=self.device)
         lv_all = torch.empty(K, B, self.ns, device=self.device)
         lp_all = torch.empty(K, B, self.na, device=self.device)
-        unroll = []
+        unroll = []  # per step: (prediction saved, dynamics saved)
         cdyn = self.dyn_block.cin_p
         crossing = [lp_all, lv_all]
         for k in range(K):
-            # prediction(h_k) (side stream)
-            p_in, psv = h, []
-            xp = h
-            self._materialize(h)
-            crossing.append(h)
+            # prediction(h_k) (side stream); h_k is a scale output: nothing owed
+            crossing.append(h.t)
             with self._side():
-                for r in self.pred_res:
-                    xp, sv = self._res_fwd(r, xp, B, hl, wl)
-                    psv.append(sv)
-                yp, spol = self._block_fwd(self.pred_pconv, xp, B, hl, wl)
-                self._linear(self.pred_plin[0], yp, B, self.pred_plin[1], self.na, lp_all[k])
-                yv, sval = self._block_fwd(self.pred_vconv, xp, B, hl, wl)
-                self._linear(self.pred_vlin[0], yv, B, self.pred_vlin[1], self.ns, lv_all[k])
+                pu = self._pred_fwd(h, B, lp_all[k], lv_all[k])
             # dynamics(h_k, a_k)
             xin = self._act(B * HWl, cdyn)
-            self._materialize(h)
-            L.call("mzba_dyn_input", self.dt, L.ptr(h), L.ptr(g["future_actions"]), L.ptr(slots), K, k, L.ptr(xin),
+            L.call("mzba_dyn_input", self.dt, L.ptr(h.t), L.ptr(g["future_actions"]), L.ptr(slots), K, k, L.ptr(xin),
                    B, HWl, self.c1, self.A, cdyn, s)
-            xd, sblk = self._block_fwd(self.dyn_block, xin, B, hl, wl)
-            dsv = []
-            for r in self.dyn_res:
-                xd, sv = self._res_fwd(r, xd, B, hl, wl)
-                dsv.append(sv)
-            yr, srew = self._block_fwd(self.dyn_rconv, xd, B, hl, wl)
-            self._linear(self.dyn_rlin[0], yr, B, self.dyn_rlin[1], self.ns, lr_all[k])
-            h_next, ssc = self._scale_fwd(xd, B)
-            unroll.append(dict(p_in=p_in, psv=psv, xp=xp, spol=spol, sval=sval, yp=yp, yv=yv, sblk=sblk, dsv=dsv,
-                               xd=xd, yr=yr, srew=srew, ssc=ssc))
-            h = h_next
+            h, du = self._dyn_fwd(_Val(xin), B, lr_all[k])
+            unroll.append((pu, du))
         self._join(*crossing)
-        for y in [e[0] for e in self._lazy.values()]:  # every BN output the backward reads exists
-            self._materialize(y)
+        self._settle()  # every BN output the backward reads exists
         # ---- loss_fn
         dlr, dlv, dlp = torch.empty_like(lr_all), torch.empty_like(lv_all), torch.empty_like(lp_all)
         loss = torch.empty(4, device=self.device)
@@ -854,17 +922,7 @@ class Learner:
         gps, crossing = [None] * K, [dlp, dlv]
         with self._side():
             for k in reversed(range(K)):
-                u = unroll[k]
-                dyv = self._linear_bwd(self.pred_vlin[0], u["yv"], dlv[k], B, self.pred_vlin[1], self.ns)
-                gp = self._block_bwd(self.pred_vconv, u["sval"], dyv, B, hl, wl)
-                dyp = self._linear_bwd(self.pred_plin[0], u["yp"], dlp[k], B, self.pred_plin[1], self.na)
-                pcons = [self._res_in_bn(r, sv) for r, sv in zip(self.pred_res, u["psv"])]
-                self._block_bwd(self.pred_pconv, u["spol"], dyp, B, hl, wl, acc=gp, nxt=pcons[-1] if pcons else None)
-                del dyv, dyp
-                for i in reversed(range(len(self.pred_res))):
-                    gp = self._res_bwd(self.pred_res[i], u["psv"][i], gp, None, B, hl, wl,
-                                       nxt=pcons[i - 1] if i > 0 else None)
-                self._materialize_b(gp)
+                gp = self._pred_bwd(unroll[k][0], dlp[k], dlv[k], B).t
                 gps[k] = gp
                 if self.streams == 2:
                     ev = torch.cuda.Event()
@@ -873,52 +931,22 @@ class Learner:
                 crossing.append(gp)
         gh = None  # gradient of h_{k+1} (scaled latent)
         for k in reversed(range(K)):
-            u = unroll[k]
-            # dynamics k: scale -> reward head -> res blocks -> conv block
-            gx = self._scale_bwd(u["ssc"], gh, B) if gh is not None else None
-            dyr = self._linear_bwd(self.dyn_rlin[0], u["yr"], dlr[k], B, self.dyn_rlin[1], self.ns)
-            xb, tb, sb, yb = u["sblk"]
-            dcons = [(self.dyn_block, yb, tb, sb)] + [self._res_in_bn(r, sv) for r, sv in zip(self.dyn_res, u["dsv"])]
-            gx = self._block_bwd(self.dyn_rconv, u["srew"], dyr, B, hl, wl, acc=gx, nxt=dcons[-1])
-            del dyr
-            for i in reversed(range(len(self.dyn_res))):
-                gx = self._res_bwd(self.dyn_res[i], u["dsv"][i], gx, None, B, hl, wl, nxt=dcons[i])
-            gh = self._block_bwd(self.dyn_block, u["sblk"], gx, B, hl, wl)  # d h_k (first c1 channels)
-            del gx
-            self._materialize_b(gh)
+            gh = self._dyn_bwd(unroll[k][1], gh, dlr[k], B)  # d h_k, dynamics part
             gp = gps[k]
             if isinstance(gp, tuple):
                 gp, ev = gp
                 torch.cuda.current_stream(self.device).wait_event(ev)
-            L.call("mzba_axpy", self.dt, L.ptr(gh), L.ptr(gp), gh.numel(), s)  # d h_k += prediction part
+            L.call("mzba_axpy", self.dt, L.ptr(gh.t), L.ptr(gp), gh.t.numel(), s)  # d h_k += prediction part
             gps[k] = None
             unroll[k] = None
         self._join(*crossing)
-        for dt in [e[0] for e in self._lazyb.values()]:
-            self._materialize_b(dt)
+        self._settle()
         # every latent weight gradient, beside the representation backward (not earlier: the 256-workgroup
         # contractions beside the dynamics chain slow the chain more than they gain, 32.5 vs 33.2 ms)
         if self._pending:
             with self._side():
                 self._flush_wgrad(B)
-        # representation: scale -> [pool | res | conv] reversed
-        gx = self._scale_bwd(rep_scale, gh, B)
-        for ti in reversed(range(len(tape))):
-            kind, mod, sv = tape[ti]
-            prev = tape[ti - 1] if ti > 0 else None
-            nxt = self._res_in_bn(prev[1], prev[2][0]) if prev is not None and prev[0] == "res" else None
-            if kind == "pool":
-                hh2, ww2, C = sv
-                dx = self._act(B * hh2 * ww2, C)
-                L.call("mzba_avgpool2_backward", self.dt, L.ptr(gx), L.ptr(dx), B, hh2, ww2, C, s)
-                gx = dx
-            elif kind == "res":
-                svr, hh2, ww2 = sv
-                gx = self._res_bwd(mod, svr, gx, None, B, hh2, ww2, nxt=nxt)
-            else:
-                xin, hh2, ww2 = sv
-                self._wgrad(mod, xin, gx, B, hh2, ww2)
-                gx = self._dgrad(mod, gx, B, hh2, ww2) if mod is not self.rep[0][1] else None
+        self._rep_bwd(rep_saved, gh, B)
         self._join()
         # ---- Adam (networks.py:268)
         self.step_count += 1
@@ -932,9 +960,9 @@ class Learner:
 
     # -- the three nets one call at a time (the drop-in agent's train mode: RLSystem._training_stage calls
     # create_hidden_state_root / evaluate_state / hidden_state_transition itself, train_torch.py:487-528, and
-    # back-propagates its own loss_fn through them). The same launches as _minibatch_body's forward and backward
-    # pieces, on one stream with immediate weight gradients; gradients accumulate into G until zero_grad().
-    # Activations NHWC rows [B * H * W][C] of this learner's dtype; each forward returns what its backward needs.
+    # back-propagates its own loss_fn through them). The per-net functions _minibatch_body calls, on one stream
+    # with immediate weight gradients and nothing owed between calls; gradients accumulate into G until zero_grad().
+    # Plain tensors in and out: NHWC rows [B * H * W][C] of this learner's dtype, logits f32.
     def begin_calls(self):
         """Per-call mode: one stream, no deferred weight gradients, per-step packs from the current weights."""
         if self.streams != 1 or self.defer_wgrad or self.fuse_bn and self.dt == 1:
@@ -945,69 +973,22 @@ class Learner:
 
     def rep_forward(self, x, B):
         """RepresentationNetwork + _scale_state (networks.py:38-99, 314-328) in train mode; x [B*H*W][cin_p]."""
-        s = L.stream()
-        tape, h, hh, ww = [], x, 16, 20
-        for kind, mod in self.rep:
-            if kind == "conv":
-                y, _ = self._conv(mod, h, B, hh, ww)
-                tape.append(("conv", mod, (h, hh, ww)))
-                h = y
-            elif kind == "res":
-                h, sv = self._res_fwd(mod, h, B, hh, ww)
-                tape.append(("res", mod, (sv, hh, ww)))
-            else:
-                y = self._act(B * (hh // 2) * (ww // 2), h.shape[1])
-                L.call("mzba_avgpool2", self.dt, L.ptr(h), L.ptr(y), B, hh, ww, h.shape[1], s)
-                tape.append(("pool", None, (hh, ww, h.shape[1])))
-                h, hh, ww = y, hh // 2, ww // 2
-        h, sc = self._scale_fwd(h, B)
-        return h, (tape, sc)
+        h, saved = self._rep_fwd(_Val(x), B)
+        return h.t, saved
 
     def rep_backward(self, saved, gh, B):
         """Weight gradients of the representation from d(scaled root latent) gh."""
-        tape, sc = saved
-        s = L.stream()
-        gx = self._scale_bwd(sc, gh, B)
-        for ti in reversed(range(len(tape))):
-            kind, mod, sv = tape[ti]
-            if kind == "pool":
-                hh2, ww2, C = sv
-                dx = self._act(B * hh2 * ww2, C)
-                L.call("mzba_avgpool2_backward", self.dt, L.ptr(gx), L.ptr(dx), B, hh2, ww2, C, s)
-                gx = dx
-            elif kind == "res":
-                svr, hh2, ww2 = sv
-                gx = self._res_bwd(mod, svr, gx, None, B, hh2, ww2)
-            else:
-                xin, hh2, ww2 = sv
-                self._wgrad(mod, xin, gx, B, hh2, ww2)
-                gx = self._dgrad(mod, gx, B, hh2, ww2) if mod is not self.rep[0][1] else None
+        self._rep_bwd(saved, _Val(gh), B)
 
     def pred_forward(self, h, B):
         """PredictionNetwork (networks.py:170-241) in train mode -> (policy logits [B][na], value logits [B][ns])."""
-        hl, wl = self.lat
-        xp, psv = h, []
-        for r in self.pred_res:
-            xp, sv = self._res_fwd(r, xp, B, hl, wl)
-            psv.append(sv)
         lp = torch.empty(B, self.na, device=self.device)
         lv = torch.empty(B, self.ns, device=self.device)
-        yp, spol = self._block_fwd(self.pred_pconv, xp, B, hl, wl)
-        self._linear(self.pred_plin[0], yp, B, self.pred_plin[1], self.na, lp)
-        yv, sval = self._block_fwd(self.pred_vconv, xp, B, hl, wl)
-        self._linear(self.pred_vlin[0], yv, B, self.pred_vlin[1], self.ns, lv)
-        return lp, lv, dict(psv=psv, spol=spol, sval=sval, yp=yp, yv=yv)
+        return lp, lv, self._pred_fwd(_Val(h), B, lp, lv)
 
     def pred_backward(self, u, dlp, dlv, B):
         """-> d h from the policy / value logit gradients (each [B][n] f32)."""
-        hl, wl = self.lat
-        dyv = self._linear_bwd(self.pred_vlin[0], u["yv"], dlv.contiguous(), B, self.pred_vlin[1], self.ns)
-        gp = self._block_bwd(self.pred_vconv, u["sval"], dyv, B, hl, wl)
-        dyp = self._linear_bwd(self.pred_plin[0], u["yp"], dlp.contiguous(), B, self.pred_plin[1], self.na)
-        self._block_bwd(self.pred_pconv, u["spol"], dyp, B, hl, wl, acc=gp)
-        for i in reversed(range(len(self.pred_res))):
-            gp = self._res_bwd(self.pred_res[i], u["psv"][i], gp, None, B, hl, wl)
-        return gp
+        return self._pred_bwd(u, dlp.contiguous(), dlv.contiguous(), B).t
 
     def dyn_forward(self, h, planes, B):
         """DynamicsNetwork + _scale_state (networks.py:103-167, 282-298) in train mode on concat(h, action planes);
@@ -1017,26 +998,13 @@ class Learner:
         xin = torch.zeros(B * hl * wl, cdyn, dtype=self.tdtype, device=self.device)
         xin[:, :self.c1] = h
         xin[:, self.c1:self.c1 + self.A] = planes.reshape(B * hl * wl, self.A).to(self.tdtype)
-        xd, sblk = self._block_fwd(self.dyn_block, xin, B, hl, wl)
-        dsv = []
-        for r in self.dyn_res:
-            xd, sv = self._res_fwd(r, xd, B, hl, wl)
-            dsv.append(sv)
         lr = torch.empty(B, self.ns, device=self.device)
-        yr, srew = self._block_fwd(self.dyn_rconv, xd, B, hl, wl)
-        self._linear(self.dyn_rlin[0], yr, B, self.dyn_rlin[1], self.ns, lr)
-        h_next, ssc = self._scale_fwd(xd, B)
-        return h_next, lr, dict(sblk=sblk, dsv=dsv, yr=yr, srew=srew, ssc=ssc)
+        h_next, u = self._dyn_fwd(_Val(xin), B, lr)
+        return h_next.t, lr, u
 
     def dyn_backward(self, u, gh_next, dlr, B):
         """-> d h (the latent part of the dynamics input) from d(next scaled latent) (or None) and d(reward logits)."""
-        hl, wl = self.lat
-        gx = self._scale_bwd(u["ssc"], gh_next, B) if gh_next is not None else None
-        dyr = self._linear_bwd(self.dyn_rlin[0], u["yr"], dlr.contiguous(), B, self.dyn_rlin[1], self.ns)
-        gx = self._block_bwd(self.dyn_rconv, u["srew"], dyr, B, hl, wl, acc=gx)
-        for i in reversed(range(len(self.dyn_res))):
-            gx = self._res_bwd(self.dyn_res[i], u["dsv"][i], gx, None, B, hl, wl)
-        return self._block_bwd(self.dyn_block, u["sblk"], gx, B, hl, wl)
+        return self._dyn_bwd(u, None if gh_next is None else _Val(gh_next), dlr.contiguous(), B).t
 
     def adam_step(self):
         """Adam(lr, weight_decay=1e-4) on the accumulated gradients (networks.py:268, torch's single-tensor

@@ -768,6 +768,57 @@ def test_learner_bn_fin_tracks_separate_finalisers():
         torch.testing.assert_close(a, b, rtol=2e-3, atol=1e-5)
 
 
+@pytest.mark.parametrize("fuse_fin", [False, True])
+def test_learner_masked_gradient_reaches_only_its_own_bn(fuse_fin):
+    """A gradient that a conv_lat launch masked for BatchNorm A (with A's partial sums, and with fuse_fin already
+    A's dgamma / dbeta) says so: the backward of another BatchNorm B of the same width refuses it (RuntimeError,
+    B's dgamma / dbeta untouched: mzba_bn_backward over it would count sums a second time), and A's own backward
+    takes the partials path and adds to A's dgamma / dbeta once: equal to mzba_bn_backward on copies of the same
+    inputs within that pair's f32 rounding (_conv_lat_bn_case's tolerances; observed |dgamma| 17.2, difference
+    1.9e-6). latent_channels 128, 8 windows: the smallest conv_lat launch with partials."""
+    from mzba import _lib as L
+    from mzba.config import learner_model_cfg
+    from mzba.learner import Learner, _Val
+    from mzba.weights import init_state_dict
+    mcfg = learner_model_cfg()
+    mcfg["latent_channels"] = [128, 128]
+    B, (H, W) = 8, mcfg["latent_resolution"]
+    ring = _random_ring(B, mcfg["state_history_length"], 1, 31)
+    ln = Learner(mcfg, init_state_dict(mcfg, 2), K=1, dtype="bf16", fuse_bn=True, streams=1, fuse_fin=fuse_fin)
+    ln.train_minibatch(ring, ring.slots())  # weight packs, scratch
+    ln.G.zero_()
+    dev, M, C = ln.device, B * H * W, 128
+    g = torch.Generator().manual_seed(17)
+    c1, c2 = r = ln.dyn_res[0]  # BN A = c1's (output a1), BN B = c2's (output out)
+    _, (x, t1, a1, s1, t2, s2, out) = ln._res_fwd(r, _Val(torch.randn(M, C, generator=g).to(torch.bfloat16).to(dev)),
+                                                  B, H, W)
+    ln._settle()
+    dy = _Val(torch.randn(M, C, generator=g).to(torch.bfloat16).to(dev))
+    da1 = ln._dgrad(c2, dy, B, H, W, bn=(c1, a1, t1, s1))
+    assert da1.masked is not None  # the launch carried A's partials
+    with pytest.raises(RuntimeError):
+        ln._bn_bwd(c2, da1, out, t2, s2)
+    torch.cuda.synchronize()
+    assert int((c2.dgamma != 0).sum()) == 0 and int((c2.dbeta != 0).sum()) == 0
+    g_ref, dx_ref = da1.t.clone(), torch.empty_like(t1)
+    dg_ref, db_ref = torch.zeros(C, device=dev), torch.zeros(C, device=dev)
+    ws = torch.empty(((M + 63) // 64) * C * 8 + 12 * C, dtype=torch.uint8, device=dev)
+    L.call("mzba_bn_backward", 1, L.ptr(g_ref), L.ptr(a1.t), L.ptr(t1), L.ptr(s1), M, C, L.ptr(dg_ref), L.ptr(db_ref),
+           L.ptr(dx_ref), L.ptr(ws), ws.numel(), L.stream())
+    dt1 = ln._bn_bwd(c1, da1, a1, t1, s1)
+    assert dt1.owed is not None and da1.masked is None  # the partials path: the apply is left to the consumer
+    dx = dt1.ready()
+    torch.cuda.synchronize()
+    assert torch.equal(g_ref, da1.t)  # it was already A's masked gradient
+    print("dgamma", c1.dgamma.abs().max().item(), (c1.dgamma - dg_ref).abs().max().item(),
+          "dbeta", c1.dbeta.abs().max().item(), (c1.dbeta - db_ref).abs().max().item())
+    assert dg_ref.abs().max().item() > 0.1  # once and twice are far apart at this tolerance
+    torch.testing.assert_close(c1.dgamma, dg_ref, rtol=1e-4, atol=1e-3)
+    torch.testing.assert_close(c1.dbeta, db_ref, rtol=1e-4, atol=1e-3)
+    assert (dx.float() - dx_ref.float()).abs().max().item() <= 1e-2 * dx_ref.float().abs().max().item()
+    assert int((c2.dgamma != 0).sum()) == 0 and int((c2.dbeta != 0).sum()) == 0
+
+
 def test_learner_fused_bn_statistics_track_separate_passes():
     """bf16 learner with the BN statistics in the conv epilogues vs the separate BN passes. The per-kernel
     arithmetic is checked deterministically by test_conv_lat_bn_matches_separate_passes (partial
