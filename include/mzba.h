@@ -187,7 +187,8 @@ int mzba_conv_halo(const void* in, const void* wh, const float* bias, const void
  * DESIGN.md §conv_lat); a workgroup keeps E = 160/(H*W) envs' activations in LDS. */
 int mzba_conv_lat_supported(int H, int W, int Cin, int Cout, int ks);
 /* Kernel shape selection for A/B experiments (0 = default 8-wave kernel, with 3-row-tile workgroups
- * where the 5-tile grid would leave CUs idle; 1 = 4-wave 2-tile kernel; 2 = 5-row-tile workgroups only). */
+ * where the 5-tile grid would leave CUs idle; 2 = 5-row-tile workgroups only; 3 = 3-row-tile workgroups wherever they
+ * apply, two per CU). -1 for another value (1, a 4-wave 2-tile experiment, was retired). */
 int mzba_conv_lat_set_variant(int v);
 /* current conv_lat variant (the learner switches to 5-row tiles for its two-stream minibatch and back) */
 int mzba_conv_lat_get_variant(void);
@@ -527,8 +528,9 @@ int mzba_conv_pack_bf16_multi(const float* const* w, void* const* out, const int
 /* Conv2d weight / bias gradient: dw [Cout][ks*ks][Cin] += sum_m dy[m][co] * x_tap[m][ci],
  * db [Cout] += sum_m dy[m][co] (db may be NULL). x NHWC [B][H][W][Cin], dy [B][H][W][Cout]. */
 long long mzba_conv_wgrad_ws_bytes(int B, int H, int W, int Cin, int Cout, int ks);
-/* bf16 3x3 weight-gradient kernel choice: 1 (default) whole zero-bordered images per tile, all 9 taps;
- * 0 one tap per tile (the kernel used for 1x1 and f32). */
+/* bf16 3x3 weight-gradient kernel choice: 1 (default) the whole-image kernel (a tile takes all 9 taps over the pixel
+ * rows of whole images) where it wins; 2 that kernel for every shape its plan accepts; 0 one tap per tile (the
+ * kernel used for 1x1 and f32). */
 int mzba_conv_wgrad_set_variant(int v);
 /* the whole-image kernel's form (per host thread): 2 (default) pixel rows with 64-co wave tiles — k over the
  * real pixels of a stage, out-of-image taps read a zero row (round 6); 1 the same with 32-co wave tiles

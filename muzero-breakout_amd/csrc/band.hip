@@ -45,13 +45,6 @@ struct BandArgs {
   int B, relu;
 };
 
-#ifndef BAND_ONEPASS
-#define BAND_ONEPASS 1  // 0: the three per-shift k loops (band_dx) everywhere, for A/B builds
-#endif
-#ifndef BAND_ONEPASS128
-#define BAND_ONEPASS128 1  // the Cout 128 convs on the one pass too (3-entry ring at 5 columns); 0: A/B build
-#endif
-
 #ifdef BAND_STAMPS
 // diagnostic build only (make band-stamps -> libmzba_bstamp.so, tools/stamp_band.py): s_memtime at the
 // phase boundaries, per workgroup and wave: 0 entry, 1 band staged, 2 k loop done, 3 residual staged,
@@ -72,14 +65,10 @@ MZ_DEV void bstamp(int k, bool real = false) {
 
 template <int CIN, int COUT, int XT>
 struct BandGeo {
-  // weight ring depth (k steps; 2 at two workgroups per CU). Ring slot = step % TDB is taken as
-  // c % TDB inside a tap, so TDB must divide the NC = Cin / 32 steps of a tap
-  static constexpr int TDB = (XT == 10 ? 4 : 2) < CIN / 32 ? (XT == 10 ? 4 : 2) : CIN / 32;
-  static_assert((CIN / 32) % TDB == 0, "ring slot restarts at every tap");
   static constexpr int NSRC = XT + 2;              // staged source columns (with the halo)
   // one-pass weight ring (band_all): 3 entries (dx = -1, 0, +1) per k step; two steps in flight, one
   // where two workgroups per CU leave 256 registers per lane for 4 column tiles (6 entries spilled 52)
-  static constexpr int RDB = (XT == 5 && (COUT == 256 || BAND_ONEPASS128)) ? 3 : 6;
+  static constexpr int RDB = XT == 5 ? 3 : 6;
   // LDS bytes per source row: at Cin 64 the row is padded to 128 channels, so a chunk index XORed
   // with the 4-bit row key stays inside the row (staging and reads use the same mapping; the pad
   // chunks are never read)
@@ -95,79 +84,10 @@ struct BandGeo {
   static constexpr int BYTES = IN_BYTES > OUT_BYTES ? IN_BYTES : OUT_BYTES;
 };
 
-// the 3 dy x NC k steps of column shift DX
-template <int CIN, int COUT, int XT, int DX>
-__device__ __forceinline__ void band_dx(const uint8_t* __restrict__ lds, __amdgpu_buffer_rsrc_t wrs,
-                                        uint4 (&bq)[COUT / 64][BandGeo<CIN, COUT, XT>::TDB], f32x4 (&acc)[XT][COUT / 64],
-                                        int lane) {
-  using G = BandGeo<CIN, COUT, XT>;
-  constexpr int CTW = G::CTW, NC = G::NC, TDB = G::TDB;
-  constexpr int SB = (DX + 1) * 3 * NC;
-  const int q = lane >> 4, ys = nib(SIG, lane & 15);
-  auto rows = [&](int dy, int& base, int& tst, int& sw) {
-    const int yy = ys + dy;
-    const bool ok = (unsigned)yy < (unsigned)BH;
-    base = ok ? ((1 + DX) * 16 + yy) * G::RB : G::LZ + (yy & 15) * G::RB;
-    tst = ok ? 16 * G::RB : 0;
-    sw = nib(KEY, yy & 15) << 4;
-  };
-  int base, tst, sw;
-  rows(-1, base, tst, sw);
-  bf16x8 afc[XT], afn[XT];
-#pragma unroll
-  for (int t = 0; t < XT; ++t) afc[t] = *reinterpret_cast<const bf16x8*>(lds + base + t * tst + ((q << 4) ^ sw));
-#pragma unroll 1
-  for (int dyi = 0; dyi < 3; ++dyi) {
-    int nbase, ntst, nsw;
-    rows(dyi < 2 ? dyi : 1, nbase, ntst, nsw);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int s = SB + dyi * NC + c;
-      bf16x8 w[CTW];
-#pragma unroll
-      for (int ct = 0; ct < CTW; ++ct) {
-        w[ct] = __builtin_bit_cast(bf16x8, bq[ct][c % TDB]);
-        bq[ct][c % TDB] = wld<G::TNS>(wrs, ct, s + TDB, lane);
-      }
-#pragma unroll
-      for (int t = 0; t < XT; ++t) {
-#pragma unroll
-        for (int ct = 0; ct < CTW; ++ct)
-          acc[t][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[ct], afc[t], acc[t][ct], 0, 0, 0);
-        if (c + 1 < NC)
-          afn[t] = *reinterpret_cast<const bf16x8*>(lds + base + t * tst + (((4 * (c + 1) + q) << 4) ^ sw));
-        else
-          afn[t] = *reinterpret_cast<const bf16x8*>(lds + nbase + t * ntst + ((q << 4) ^ nsw));
-      }
-      // every A read of the next k step in the first XT MFMA slots: the compiler orders a step's
-      // independent MFMAs freely, so the next step may open with any tile (tower.hip tower8_dx)
-#pragma unroll
-      for (int t = 0; t < XT; ++t) {
-        __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-#pragma unroll
-      for (int ct = 0; ct < CTW; ++ct) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, XT * CTW - XT - CTW, 0);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int t = 0; t < XT; ++t) afc[t] = afn[t];
-    }
-    base = nbase; tst = ntst; sw = nsw;
-  }
-}
-
-
-// the one pass runs every conv (B = 4096 isolated: 256->256 1202 -> 1131 us, 128->256 675 -> 639 us;
-// 128->128 with the 3-entry ring 368 -> 355 us). The Cout 128 convs kept the three loops in round 2
-// because their one pass moved the bf16 learner's gradients past a noise bound between two bf16
-// realisations; that bound was a lucky seed (tools/learner_bn_calib.py: 0.86 - 0.9998 over 6 seeds on
-// either build) and the learner test now checks each realisation against the f32 path instead
-template <int COUT> constexpr bool band_one = BAND_ONEPASS && (COUT == 256 || BAND_ONEPASS128);
+// Every conv runs the one k-loop pass below (band_all). The three per-shift k loops it replaced in rounds 2-3 are
+// profiles/r02/b128/band_per_shift_loops_retired.patch. The Cout 128 convs stayed on them for a round because their one pass
+// moved the bf16 learner's gradients past a noise bound between two bf16 realisations; that bound was a lucky seed
+// (tools/learner_bn_calib.py), and the learner test now checks each realisation against the f32 path instead.
 
 // pack step of one-pass ring entry e = 3 (dyi * NC + c) + d (d = dx + 1)
 template <int NC>
@@ -304,24 +224,18 @@ __global__ __launch_bounds__(BNT, XT == 10 ? 1 : 2) void band_conv_kernel(BandAr
   const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<uint4*>(reinterpret_cast<const uint4*>(a.wf) + (size_t)__builtin_amdgcn_readfirstlane(wave * CTW) * G::TNS * 64),
       0, 0x7fffffff, 0x00020000);
-  constexpr int TDB = band_one<COUT> ? G::RDB : G::TDB;
+  constexpr int TDB = G::RDB;
   uint4 bq[CTW][TDB];
 #pragma unroll
   for (int ct = 0; ct < CTW; ++ct)
 #pragma unroll
-    for (int i = 0; i < TDB; ++i) bq[ct][i] = wld<G::TNS>(wrs, ct, band_one<COUT> ? band_step<G::NC>(i) : i, lane);
+    for (int i = 0; i < TDB; ++i) bq[ct][i] = wld<G::TNS>(wrs, ct, band_step<G::NC>(i), lane);
   f32x4 acc[XT][CTW];
 #pragma unroll
   for (int t = 0; t < XT; ++t)
 #pragma unroll
     for (int ct = 0; ct < CTW; ++ct) acc[t][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if constexpr (band_one<COUT>) {
-    band_all<CIN, COUT, XT>(lds, wrs, bq, acc, lane);
-  } else {
-    band_dx<CIN, COUT, XT, -1>(lds, wrs, bq, acc, lane);
-    band_dx<CIN, COUT, XT, 0>(lds, wrs, bq, acc, lane);
-    band_dx<CIN, COUT, XT, 1>(lds, wrs, bq, acc, lane);
-  }
+  band_all<CIN, COUT, XT>(lds, wrs, bq, acc, lane);
   BSTAMP(2);
   __syncthreads();  // the band is no longer read
   // output tile in LDS: row 16 t + y, 16-B chunks swizzled by KEY[y]
@@ -404,9 +318,7 @@ __global__ __launch_bounds__(BNT, XT == 10 ? 1 : 2) void band_conv_kernel(BandAr
 // then conv2 computes the band from them, + bias + the residual (re-read from global), ReLU. The same
 // k loop as band_conv_kernel, so the outputs equal two band launches bit for bit; every weight fragment
 // feeds 12 (conv1) / 10 (conv2) MFMAs instead of 5, at 10 % recomputed halo columns.
-#ifndef BAND_RES_RDB
-#define BAND_RES_RDB 3
-#endif
+constexpr int BAND_RES_RDB = 3;
 
 struct BandResArgs {
   const bf16_t* in;   // [B][320][C]

@@ -37,13 +37,8 @@ namespace {
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-#ifndef HALO_EPI16
-#define HALO_EPI16 1  // 16-B epilogue accesses through v_permlane16_swap (0: the round-4 8-B form, an A/B build)
-#endif
-#ifndef HALO_RING
-#define HALO_RING 2  // weight ring depth in k steps (an A/B build may deepen it)
-#endif
 namespace hl {
+constexpr int RING = 2;            // weight ring depth in k steps (3 measured no faster: profiles/r05/halo_ring3/)
 constexpr int TM = 256;            // output pixels per workgroup
 constexpr int TN = 256;            // output channels per workgroup
 constexpr int NT = 512;            // 8 waves, two per SIMD
@@ -73,9 +68,8 @@ struct HaloArgs {
 // the same key as repblocks.hip's rf::key)
 MZ_DEV int hkey(int r) { return ((r << 1) & 6) | (((r >> 2) & 1) * 9); }
 
-// + bias (+ residual), ReLU, bf16: (acc + bias) + res in f32, as conv_big_bf16_kernel; a lane stores 4
-// consecutive channels (8 B) of one pixel per (pixel tile, column tile); every residual load of a pixel tile
-// is issued before its first use
+// + bias (+ residual), ReLU, bf16: (acc + bias) + res in f32, as conv_big_bf16_kernel; every residual load of a
+// pixel tile is issued before its first use
 template <bool RES, bool AB, int MT, int CT>
 MZ_DEV void halo_epilogue(const HaloArgs& a, const f32x4 (&acc)[MT][CT], int mb, int nb, int q, int n) {
   const int HW = a.H * a.W;
@@ -93,13 +87,13 @@ MZ_DEV void halo_epilogue(const HaloArgs& a, const f32x4 (&acc)[MT][CT], int mb,
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct) bb[ct] = *reinterpret_cast<const float4*>(a.bias + nb + ct * 16 + 4 * q);
   const float lo = a.relu ? 0.f : -__builtin_inff();  // ReLU as max(v, 0); max(v, -inf) = v
-#if HALO_EPI16
   // 16-B form: the k-quarter rows q = 2j and 2j + 1 of a wave hold the two 8-B halves of chunk j (channels 8j..8j + 7
   // of a 16-channel column tile) of the same pixel. For a column-tile pair (ct, ct + 1) one v_permlane16_swap per
   // dword of (acc + bias) hands the odd row's ct half to the even row and the even row's ct + 1 half to the odd
   // row: an even-row lane then owns tile ct's chunk j, an odd-row lane tile ct + 1's, and its residual load, the
   // ReLU / bf16 pack and the store are one 16-B access each (half the epilogue's memory instructions). The f32
-  // expression of every element is unchanged, so the outputs are bit-identical to the 8-B form.
+  // expression of every element is unchanged, so the outputs are bit-identical to the round-4 8-B form (a lane storing its own 4
+  // channels per column tile: profiles/r05/halo_epi16/halo_epi8_retired.patch).
   static_assert(CT % 2 == 0, "column-tile pairs");
   const int cj = 8 * (q >> 1), codd = q & 1;
 #pragma unroll
@@ -144,46 +138,6 @@ MZ_DEV void halo_epilogue(const HaloArgs& a, const f32x4 (&acc)[MT][CT], int mb,
       if (m < a.M) *reinterpret_cast<uint4*>(a.out + (size_t)m * a.Cout + nb + (2 * cp + codd) * 16 + cj) = o;
     }
   }
-#else
-#pragma unroll
-  for (int mi = 0; mi < MT; ++mi) {
-    const int m = mb + mi * 16 + n;
-    const int mc = m < a.M ? m : a.M - 1;
-    uint2 rv[CT];
-    float4 ab[CT];
-    if (AB) {
-      const bool hi = mc >= tb1;
-      const int p = mc - (hi ? tb1 : tb1 - HW), av = hi ? av1 : av0;
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct)
-        ab[ct] = *reinterpret_cast<const float4*>(a.act_bias + ((size_t)p * a.A + av) * a.Cout + nb + ct * 16 + 4 * q);
-    }
-    if (RES) {
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct) rv[ct] = *reinterpret_cast<const uint2*>(a.res + (size_t)mc * a.Cout + nb + ct * 16 + 4 * q);
-    }
-    uint2 o[CT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-      float v[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = AB ? (acc[mi][ct][i] + (&ab[ct].x)[i]) + (&bb[ct].x)[i] : acc[mi][ct][i] + (&bb[ct].x)[i];
-      if (RES) {
-        v[0] = v[0] + bf16_to_f32((bf16_t)(rv[ct].x & 0xffffu));
-        v[1] = v[1] + bf16_to_f32((bf16_t)(rv[ct].x >> 16));
-        v[2] = v[2] + bf16_to_f32((bf16_t)(rv[ct].y & 0xffffu));
-        v[3] = v[3] + bf16_to_f32((bf16_t)(rv[ct].y >> 16));
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = fmaxf(v[i], lo);
-      o[ct] = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
-    }
-    if (m < a.M) {
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct) *reinterpret_cast<uint2*>(a.out + (size_t)m * a.Cout + nb + ct * 16 + 4 * q) = o[ct];
-    }
-  }
-#endif
 }
 
 // WM = 2 pixel halves x 4 quarters of 64 channels. Measured and dropped (profiles/r04/halo_wm/, same box, B = 4096,
@@ -253,11 +207,11 @@ __global__ __launch_bounds__(64 * NW, OCC == 1 ? 1 : OCC * NW / 4) void conv_hal
   auto wload = [&](int ct, int s) {
     return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, lane * 16, (ct * KS + s) * 1024, 0));
   };
-  bf16x8 bq[HALO_RING][CT];
+  bf16x8 bq[hl::RING][CT];
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-    for (int i = 0; i < HALO_RING; ++i) bq[i][ct] = wload(ct, kstep(i));
+    for (int i = 0; i < hl::RING; ++i) bq[i][ct] = wload(ct, kstep(i));
 
   f32x4 acc[MT][CT];
 #pragma unroll
@@ -313,8 +267,9 @@ __global__ __launch_bounds__(64 * NW, OCC == 1 ? 1 : OCC * NW / 4) void conv_hal
     for (int t = 0; t < 9; ++t) {
 #pragma unroll
       for (int c = 0; c < NCS; ++c) {
-        const int sl = HALO_RING == 2 ? (c & 1) : j % HALO_RING;  // j & 1: the steps per tap (NCS) are even
-        const int sn = kstep(j + HALO_RING);
+        static_assert(hl::RING == 2 && NCS % 2 == 0, "ring slot j % RING taken as c & 1: even steps per tap");
+        const int sl = c & 1;
+        const int sn = kstep(j + hl::RING);
 #pragma unroll
         for (int mi = 0; mi < MT; ++mi) {
           const int idx = c * MT + mi, nx = idx + PF;

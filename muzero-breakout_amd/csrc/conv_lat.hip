@@ -40,7 +40,6 @@ __device__ unsigned long long mz_lat_stamps[4096][8];
 #else
 #define MZ_STAMP(k) do {} while (0)
 #endif
-constexpr int MAXROWS = 32 * R;
 
 struct LatArgs {
   const bf16_t* in;
@@ -199,7 +198,7 @@ __device__ __forceinline__ void lat_bn_finish(const LatArgs& a, float* ws, int t
 // reduced through LDS; (2) finish 16-B output chunks: + residual, ReLU, bf16, 16-B stores.
 // Bias and the per-(pixel, action) bias were folded into the accumulator init.
 constexpr int EPT_MAX = 10;
-template <int NT, int MR = MAXROWS>
+template <int NT, int MR>
 __device__ __forceinline__ void lat_res_prefetch(const LatArgs& a, uint4 (&rv)[EPT_MAX], int rows, int env0, int HW,
                                                  int tid) {
   constexpr int EPT = (MR * 16 + NT - 1) / NT;
@@ -218,7 +217,7 @@ __device__ __forceinline__ void lat_res_prefetch(const LatArgs& a, uint4 (&rv)[E
     }
   }
 }
-template <int NT, int MR = MAXROWS>
+template <int NT, int MR>
 __device__ __forceinline__ void lat_epilogue(const LatArgs& a, float* ot, const uint4 (&rv)[EPT_MAX], int rows,
                                              int env0, int HW, int tid) {
   constexpr int EPT = (MR * 16 + NT - 1) / NT;
@@ -557,27 +556,17 @@ __global__ __launch_bounds__(64 * WAVES, OCC * WAVES / 4) void conv_lat_kernel(L
       for (int c = 0; c < NH; ++c) {
         const int s = tap * NH + c;
         const uint4 bcur = bq[c % D];
-#if defined(MZ_LAT_ABLATE) && MZ_LAT_ABLATE == 1
-        bq[c % D] = wp[(size_t)((s + D) & 7) * 64];  // ablation: weights from an 8-step (8 KB) hot window
-#else
         bq[c % D] = wp[(size_t)(s + D) * 64];
-#endif
         const bf16x8 bfr = __builtin_bit_cast(bf16x8, bcur);
         // MFMA on this step's fragment, then issue the next step's read of the same row tile:
         // it has the 4 following MFMAs (~128 cycles) to land.
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
-#if defined(MZ_LAT_ABLATE) && MZ_LAT_ABLATE == 3
-          asm volatile("" ::"v"(afc[rt]), "v"(bfr));  // ablation: no MFMA
-#else
           acc[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afc[rt], bfr, acc[rt], 0, 0, 0);
-#endif
-#if !(defined(MZ_LAT_ABLATE) && MZ_LAT_ABLATE == 2)
           if (c + 1 < NH)
             afn[rt] = *reinterpret_cast<const bf16x8*>(lds + offc[rt] + (((cbase + 2 * (c + 1)) << 4) ^ swc[rt]));
           else
             afn[rt] = *reinterpret_cast<const bf16x8*>(lds + offn[rt] + ((cbase << 4) ^ swn[rt]));
-#endif
         }
         // interleave {MFMA, DS read, VALU} x R, then the weight load; the reads' consumers are
         // behind the step barrier, so no MFMA waits on a read issued in its own step
@@ -627,184 +616,6 @@ __global__ __launch_bounds__(64 * WAVES, OCC * WAVES / 4) void conv_lat_kernel(L
   MZ_STAMP(5);
 }
 
-// Variant with 2 column tiles per wave: 4 waves = 2 column halves (64 channels each) x 2
-// channel halves of every tap, one wave per SIMD (512-register budget). Each A fragment read
-// from LDS feeds 2 MFMAs (half the LDS traffic per FLOP of conv_lat_kernel). Same weight
-// packing as the 8-wave kernel (pack_lat ksplit=2).
-template <int KS, int CIN>
-__global__ __launch_bounds__(256, 1) void conv_lat2_kernel(LatArgs a) {
-  constexpr int NC = CIN / 16;
-  constexpr int NH = NC / 2;             // k steps per tap per wave
-  constexpr int NSW = KS * KS * NH;      // k steps per wave
-  constexpr int D = NH >= 8 ? 8 : NH;    // ring depth per column tile
-  constexpr int ROWB = CIN * 2;
-  constexpr int NCHUNK = CIN / 8;
-  constexpr int SMASK = NCHUNK >= 16 ? 15 : NCHUNK - 1;
-  constexpr int PAD = KS / 2;
-  constexpr int NT = 256;
-  static_assert(NH % D == 0, "ring / tap alignment");
-  constexpr int LDS_A = (MAXROWS + 1) * ROWB, LDS_C = MAXROWS * 128 * 4;
-  __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_A > LDS_C ? LDS_A : LDS_C];
-  __shared__ long long envoff[32 * R];
-  const int HW = a.H * a.W;
-  const int env0 = blockIdx.x * a.E;
-  const int nenv = min(a.E, a.B - env0);
-  const int rows = nenv * HW;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int cw = wave & 1, kh = wave >> 1;          // column half (2 tiles), channel half
-  const int ct0 = blockIdx.y * 4 + 2 * cw;           // first of this wave's two 32-column tiles
-  const bool act0 = ct0 * 32 < a.Cout, act1 = (ct0 + 1) * 32 < a.Cout;
-  MZ_STAMP(0);
-  const uint4* wp0 = reinterpret_cast<const uint4*>(a.wf) + ((size_t)(act0 ? ct0 : 0) * 2 + kh) * NSW * 64 + lane;
-  const uint4* wp1 = reinterpret_cast<const uint4*>(a.wf) + ((size_t)(act1 ? ct0 + 1 : 0) * 2 + kh) * NSW * 64 + lane;
-  uint4 bq0[D], bq1[D];
-#pragma unroll
-  for (int i = 0; i < D; ++i) { bq0[i] = wp0[(size_t)i * 64]; bq1[i] = wp1[(size_t)i * 64]; }
-  const float bias0 = a.bias[act0 ? ct0 * 32 + (lane & 31) : 0], bias1 = a.bias[act1 ? ct0 * 32 + 32 + (lane & 31) : 0];
-
-  if (tid < a.E) {
-    const int b = env0 + (tid < nenv ? tid : 0);
-    long long off = (long long)b * a.in_env_stride;
-    if (a.slot) off += (long long)a.slot[b] * a.in_slot_stride;
-    envoff[tid] = off;
-  }
-  __syncthreads();
-  constexpr int TOTAL = (MAXROWS + 1) * NCHUNK;
-  constexpr int PER = (TOTAL + NT - 1) / NT;
-  constexpr int BATCH = PER < 11 ? PER : 11;
-#pragma unroll
-  for (int base = 0; base < PER; base += BATCH) {
-    uint4 v[BATCH];
-#pragma unroll
-    for (int u = 0; u < BATCH; ++u) {
-      const int i = (base + u) * NT + tid;
-      const int r = i / NCHUNK, c = i % NCHUNK;
-      const bool ok = base + u < PER && i < TOTAL && r < rows;
-      const int rr = ok ? r : 0;
-      const int e = rr / HW, p = rr - (rr / HW) * HW;
-      v[u] = *reinterpret_cast<const uint4*>(a.in + envoff[e] + (long long)p * CIN + c * 8);
-      if (!ok) v[u] = make_uint4(0, 0, 0, 0);
-    }
-#pragma unroll
-    for (int u = 0; u < BATCH; ++u) {
-      const int i = (base + u) * NT + tid;
-      if (base + u < PER && i < TOTAL) {
-        const int r = i / NCHUNK, c = i % NCHUNK;
-        *reinterpret_cast<uint4*>(lds + r * ROWB + ((c ^ (r & SMASK)) << 4)) = v[u];
-      }
-    }
-  }
-  __syncthreads();
-  MZ_STAMP(1);
-
-  const int l32 = lane & 31, h = lane >> 5;
-  f32x16 acc0[R], acc1[R];
-#pragma unroll
-  for (int rt = 0; rt < R; ++rt)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int row = rt * 32 + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
-      acc0[rt][i] = (act0 && kh == 0) ? lat_acc_init(a, bias0, row, rows, ct0 * 32 + (lane & 31), env0, HW) : 0.f;
-      acc1[rt][i] = (act1 && kh == 0) ? lat_acc_init(a, bias1, row, rows, ct0 * 32 + 32 + (lane & 31), env0, HW) : 0.f;
-    }
-  {
-    int ry[R], rx[R], rbase[R];
-    bool rval[R];
-#pragma unroll
-    for (int rt = 0; rt < R; ++rt) {
-      const int m = rt * 32 + l32;
-      rval[rt] = m < rows;
-      const int e = m / HW, p = m - (m / HW) * HW;
-      ry[rt] = p / a.W;
-      rx[rt] = p - ry[rt] * a.W;
-      rbase[rt] = e * HW;
-    }
-    auto tap_rows = [&](int tap, int (&off)[R], int (&sw)[R]) {
-      const int ky = tap / KS - PAD, kx = tap % KS - PAD;
-#pragma unroll
-      for (int rt = 0; rt < R; ++rt) {
-        const int sy = ry[rt] + ky, sx = rx[rt] + kx;
-        const bool ok = rval[rt] && sy >= 0 && sy < a.H && sx >= 0 && sx < a.W;
-        const int r = ok ? rbase[rt] + sy * a.W + sx : MAXROWS;
-        off[rt] = r * ROWB;
-        sw[rt] = (r & SMASK) << 4;
-      }
-    };
-    const int cbase = kh * (2 * NH) + h;
-    int offc[R], swc[R], offn[R], swn[R];
-    tap_rows(0, offc, swc);
-    bf16x8 afc[R], afn[R];
-#pragma unroll
-    for (int rt = 0; rt < R; ++rt)
-      afc[rt] = *reinterpret_cast<const bf16x8*>(lds + offc[rt] + ((cbase << 4) ^ swc[rt]));
-    for (int tap = 0; tap < KS * KS; ++tap) {
-      tap_rows(tap + 1 < KS * KS ? tap + 1 : tap, offn, swn);
-#pragma unroll
-      for (int c = 0; c < NH; ++c) {
-        const int s = tap * NH + c;
-        const bf16x8 b0 = __builtin_bit_cast(bf16x8, bq0[c % D]);
-        const bf16x8 b1 = __builtin_bit_cast(bf16x8, bq1[c % D]);
-        bq0[c % D] = wp0[(size_t)(s + D) * 64];
-        bq1[c % D] = wp1[(size_t)(s + D) * 64];
-#pragma unroll
-        for (int rt = 0; rt < R; ++rt) {
-          acc0[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afc[rt], b0, acc0[rt], 0, 0, 0);
-          acc1[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afc[rt], b1, acc1[rt], 0, 0, 0);
-          if (c + 1 < NH)
-            afn[rt] = *reinterpret_cast<const bf16x8*>(lds + offc[rt] + (((cbase + 2 * (c + 1)) << 4) ^ swc[rt]));
-          else
-            afn[rt] = *reinterpret_cast<const bf16x8*>(lds + offn[rt] + ((cbase << 4) ^ swn[rt]));
-        }
-#pragma unroll
-        for (int rt = 0; rt < R; ++rt) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int rt = 0; rt < R; ++rt) afc[rt] = afn[rt];
-      }
-#pragma unroll
-      for (int rt = 0; rt < R; ++rt) { offc[rt] = offn[rt]; swc[rt] = swn[rt]; }
-    }
-  }
-
-  MZ_STAMP(3);
-  uint4 rv[EPT_MAX];
-  lat_res_prefetch<NT>(a, rv, rows, env0, HW, tid);
-  __syncthreads();
-  MZ_STAMP(4);
-  float* ot = reinterpret_cast<float*>(lds);
-  const int col0 = cw * 64 + l32;
-  if (kh == 0) {
-#pragma unroll
-    for (int rt = 0; rt < R; ++rt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        ot[row * 128 + col0] = acc0[rt][r];
-        ot[row * 128 + col0 + 32] = acc1[rt][r];
-      }
-  }
-  __syncthreads();
-  if (kh == 1) {
-#pragma unroll
-    for (int rt = 0; rt < R; ++rt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        ot[row * 128 + col0] += acc0[rt][r];
-        ot[row * 128 + col0 + 32] += acc1[rt][r];
-      }
-  }
-  __syncthreads();
-  lat_epilogue<NT>(a, ot, rv, rows, env0, HW, tid);
-  MZ_STAMP(5);
-}
-
 }  // namespace
 
 // kernel shape, see mzba_conv_lat_set_variant. Per host thread: the learner brackets a minibatch
@@ -828,12 +639,12 @@ static int lat_ncu() {
 
 // 0: 8 waves (2 per SIMD: 4 column tiles x 2 channel halves), the default (3-row-tile workgroups
 //    where the 5-tile grid would leave CUs idle);
-// 1: 4 waves with 2 column tiles each (conv_lat2_kernel, experiment). Same weight packing;
+// 1: retired (a 4-wave kernel with 2 column tiles per wave, an experiment no shape took: profiles/r07/retired/);
 // 2: the default kernel with 5-row-tile workgroups only (A/B reference);
 // 3: 3-row-tile workgroups wherever they apply, the two-workgroups-per-CU instance (OCC 2: <= 128 VGPRs, ring depth
 //    4, ~56 KiB LDS); the fused BN finaliser (ctr) keeps the one-per-CU instances (its hand-off's condition).
 int mzba_conv_lat_set_variant(int v) {
-  if (v < 0 || v > 3) return -1;
+  if (v != 0 && v != 2 && v != 3) return -1;
   g_lat_variant = v;
   return 0;
 }
@@ -882,12 +693,7 @@ static int lat_launch(LatArgs& a, hipStream_t stream) {
     else                                                                                                        \
       hipLaunchKernelGGL((conv_lat_kernel<KS_, CIN_, 8, 8, 3>), grid, dim3(512), 0, stream, a);                 \
   }
-  if (v == 1) {
-    if (a.smode) return -4;  // the fused statistics ride on the 8-wave kernel only
-    if (ks == 3 && Cin == 256) hipLaunchKernelGGL((conv_lat2_kernel<3, 256>), grid, dim3(256), 0, stream, a);
-    else if (ks == 1 && Cin == 256) hipLaunchKernelGGL((conv_lat2_kernel<1, 256>), grid, dim3(256), 0, stream, a);
-    else return -4;
-  } else if (rt3) {
+  if (rt3) {
     MZ_LAT3(3, 256) else MZ_LAT3(1, 256) else MZ_LAT3(3, 128) else MZ_LAT3(1, 128)
   } else {
     MZ_LAT(3, 256, 8, 8) else MZ_LAT(1, 256, 8, 8) else MZ_LAT(3, 128, 8, 8) else MZ_LAT(1, 128, 8, 8)
@@ -939,7 +745,7 @@ int mzba_conv_lat_bn(const void* in, const void* wf, const float* bias, const vo
 // BN's stats [4][Cout] and updates its running statistics (run_mean / run_var optional) as mzba_bn_stats_final does;
 // mode 2 reads its stats and adds to dgamma / dbeta and writes coef [3][Cout] as mzba_bn_backward_coef does. ctr:
 // Cout / 128 unsigned words, zero at entry and zero again at exit (the launch's last workgroups reset them), never
-// shared by two launches in flight. The 8-wave kernels only (variant 0 / 2).
+// shared by two launches in flight.
 int mzba_conv_lat_bn_fin(const void* in, const void* wf, const float* bias, const void* res, void* out, int B, int H,
                          int W, int Cin, int Cout, int ks, int mode, float* part, const void* y, const void* x,
                          const float* mean, const float* pstats, const void* pres, int prelu, void* pout,
@@ -950,7 +756,7 @@ int mzba_conv_lat_bn_fin(const void* in, const void* wf, const float* bias, cons
   MZ_CHECK_ARG(Cout % 128 == 0 && part && (mode == 1 || (mode == 2 && y && x && mean)), -3);
   MZ_CHECK_ARG(!pstats || pout, -3);
   MZ_CHECK_ARG(!pcoef || (pstats && pres), -3);
-  MZ_CHECK_ARG(ctr && fstats && g_lat_variant != 1, -3);
+  MZ_CHECK_ARG(ctr && fstats, -3);
   MZ_CHECK_ARG(mode == 1 ? (gamma && beta && (!run_mean || run_var)) : (dgamma && dbeta && coef), -3);
   LatArgs a{(const bf16_t*)in, (long long)H * W * Cin, nullptr, 0, (const bf16_t*)wf, bias, nullptr, nullptr, 0,
             (const bf16_t*)res, (bf16_t*)out, B, H, W, Cin, Cout, ks, 0, 0,

@@ -216,13 +216,9 @@ __global__ void env_reset_compact_kernel(Compact cs, uint8_t* __restrict__ cur_f
 // one 16-B chunk of a rendered frame: a non-temporal store (written once, read by a later launch
 // at most once: 84x84 B=4096 10.3 -> 8.6 us per graph-replayed step)
 MZ_DEV void frame_store(uint8_t* p, uint4 v) {
-#ifndef MZ_ENV_TEMPORAL
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   u32x4 w = {v.x, v.y, v.z, v.w};
   __builtin_nontemporal_store(w, reinterpret_cast<u32x4*>(p));
-#else
-  *reinterpret_cast<uint4*>(p) = v;
-#endif
 }
 
 // Phase 1: one thread per env, all rules on the compact state (same op order as above).

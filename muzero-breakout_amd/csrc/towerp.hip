@@ -35,11 +35,9 @@
 #include "tree_dev.h"
 #include "elt.h"  // Elt<EL>: bf16 (EL 0) / fp16 (EL 1, the fp16 dynamics net of config 5) images and weights
 
-#ifndef TP_STAGE
-#define TP_STAGE 2  // staging batches per wave (2: two envs' 20 loads in flight at a time; 1: all four)
-#endif
-
 namespace {
+
+constexpr int TP_STAGE = 2;  // staging batches per wave (2: two envs' 20 loads in flight at a time; 1: all four)
 
 namespace tp {
 constexpr int E = 16;                  // envs per workgroup

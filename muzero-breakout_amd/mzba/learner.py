@@ -861,7 +861,7 @@ class Learner:
         shapes it recorded."""
         prev = L.lib().mzba_conv_lat_get_variant()
         want = {5: 2, 3: 3}.get(self.lat_rows, 0)
-        if prev not in (0, 2, 3) or prev == want:
+        if prev == want:
             return self._minibatch_body(ring, slots)
         L.call("mzba_conv_lat_set_variant", want)
         try:

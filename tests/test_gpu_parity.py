@@ -1531,6 +1531,8 @@ def test_conv_lat_vs_torch(B, H, W, Cin, Cout, ks):
     out5 = torch.empty_like(out)
     L.call("mzba_conv_lat_set_variant", 2)
     try:
+        # the retired 4-wave variant is refused and leaves the selection as it was
+        assert L.lib().mzba_conv_lat_set_variant(1) == -1 and L.lib().mzba_conv_lat_get_variant() == 2
         L.call("mzba_conv_lat", L.ptr(d["pool"]), S1 * H * W * Cin, L.ptr(d["slot"]), H * W * Cin, L.ptr(wf),
                L.ptr(d["b"]), L.ptr(d["ab"]), L.ptr(d["act"]), A, L.ptr(d["res"]), L.ptr(out5), B, H, W, Cin,
                Cout, ks, 1, L.stream())

@@ -1,5 +1,5 @@
 """Phase breakdown of conv_lat from in-kernel s_memtime stamps (diagnostic build only).
-`python tools/stamp_conv.py [variants|ablate|learner|mfma|zrows|libs TAG...]`. Stamps: 0 entry, 1 after staging barrier, 3 wave0 after main loop (7 = wave 4), 4 after the
+`python tools/stamp_conv.py [variants|learner|zrows|libs TAG...]`. Stamps: 0 entry, 1 after staging barrier, 3 wave0 after main loop (7 = wave 4), 4 after the
 post-loop barrier, 5 end. Shares are what count (the stamps' fences perturb timing)."""
 import ctypes
 import json
@@ -77,33 +77,15 @@ if __name__ == "__main__":
                     for s in [(512, 4, 5, 256, 256, 3), (1024, 4, 5, 256, 256, 3)]:
                         print(json.dumps({"zero_rows": 1 if tag else 16, "rep": rep, "lat_variant": v, "shape": s,
                                           "cycles": run(D, *s)}), flush=True)
-    elif which == "mfma":  # 16x16x32 vs 32x32x16 MFMAs at the learner's shapes, alternated (needs the A/B build of
-        # profiles/r05/lat_mfma16/conv_lat_mfma16_rejected.patch: mzba_conv_lat_set_mfma)
-        D = load("")
-        D.mzba_conv_lat_set_mfma.argtypes = [I]
-        for rep in range(2):
-            for mf in (32, 16):
-                assert D.mzba_conv_lat_set_mfma(mf) == 0
-                for v in (0, 2):
-                    assert D.mzba_conv_lat_set_variant(v) == 0
-                    for s in [(512, 4, 5, 256, 256, 3), (1024, 4, 5, 256, 256, 3)]:
-                        print(json.dumps({"mfma": mf, "rep": rep, "lat_variant": v, "shape": s, "cycles": run(D, *s)}),
-                              flush=True)
     elif which == "learner":  # the learner's B = 512 latent conv: 3-row (variant 0) and 5-row (2) tiles
-        for tag, name in (("", "full"), ("_a1", "hot 8KB weights"), ("_a2", "no LDS A reads"), ("_a3", "no MFMA")):
-            D = load(tag)
-            for v in (0, 2):
-                assert D.mzba_conv_lat_set_variant(v) == 0
-                for s in [(512, 4, 5, 256, 256, 3), (1024, 4, 5, 256, 256, 3)]:
-                    print(json.dumps({"variant": name, "lat_variant": v, "shape": s, "cycles": run(D, *s)}), flush=True)
-    elif which == "ablate":
-        for tag, name in (("", "full"), ("_a1", "hot 8KB weights"), ("_a2", "no LDS A reads"), ("_a3", "no MFMA")):
-            D = load(tag)
-            for s in [(1024, 4, 5, 256, 256, 3), (1024, 4, 5, 256, 256, 1)]:
-                print(json.dumps({"variant": name, "shape": s, "cycles": run(D, *s)}))
+        D = load("")
+        for v in (0, 2):
+            assert D.mzba_conv_lat_set_variant(v) == 0
+            for s in [(512, 4, 5, 256, 256, 3), (1024, 4, 5, 256, 256, 3)]:
+                print(json.dumps({"lat_variant": v, "shape": s, "cycles": run(D, *s)}), flush=True)
     else:
         D = load("")
-        for v, name in ((0, "8w ring8"), (1, "4w 2ct/wave")):
+        for v, name in ((0, "auto rows"), (2, "5-row tiles"), (3, "3-row tiles, two per CU")):
             assert D.mzba_conv_lat_set_variant(v) == 0
             for s in [(1024, 4, 5, 256, 256, 3), (4096, 4, 5, 256, 256, 3)]:
                 print(json.dumps({"variant": name, "shape": s, "cycles": run(D, *s)}))
