@@ -484,7 +484,7 @@ int mzba_ctx_advance(int32_t* ctx, hipStream_t stream);
 
 /* BatchNorm2d forward statistics in train mode (nn.BatchNorm2d in ConvBlock / ResidualBlock,
  * networks.py:7-35): stats[4][C] = (mean, invstd, gamma*invstd, beta - mean*gamma*invstd) over the
- * M rows of x [M][C]; running_mean / running_var (may be NULL) updated with momentum and the
+ * M rows of x [M][C]; running_mean / running_var (both or neither NULL) updated with momentum and the
  * unbiased variance. C % 4 == 0; ws >= ceil(M/64)*C*8 bytes. */
 int mzba_bn_stats(int dtype, const void* x, int M, int C, float eps, float momentum, const float* gamma,
                   const float* beta, float* stats, float* run_mean, float* run_var, void* ws, long long ws_bytes,
@@ -546,7 +546,7 @@ int mzba_conv_wgrad(int dtype, const void* x, const void* dy, int B, int H, int 
 int mzba_conv_wgrad_segs(int dtype, const void* const* xs, const void* const* dys, int nseg, int B, int H, int W,
                          int Cin, int Cout, int ks, float* dw, float* db, void* ws, long long ws_bytes,
                          hipStream_t stream);
-/* nn.AvgPool2d(2, 2) backward: dx [B][H][W][C] = dy[y/2][x/2] / 4. */
+/* nn.AvgPool2d(2, 2) backward: dx [B][H][W][C] = dy[y/2][x/2] / 4. H, W even; B, H, W, C > 0. */
 int mzba_avgpool2_backward(int dtype, const void* dy, void* dx, int B, int H, int W, int C, hipStream_t stream);
 /* y += x (n elements). */
 int mzba_axpy(int dtype, void* y, const void* x, long long n, hipStream_t stream);

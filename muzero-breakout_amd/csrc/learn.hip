@@ -1644,7 +1644,7 @@ extern "C" {
 int mzba_bn_stats(int dtype, const void* x, int M, int C, float eps, float momentum, const float* gamma,
                   const float* beta, float* stats, float* run_mean, float* run_var, void* ws, long long ws_bytes,
                   hipStream_t stream) {
-  MZ_CHECK_ARG(x && stats && gamma && beta && ws && M > 0 && C > 0 && C % 4 == 0, -1);
+  MZ_CHECK_ARG(x && stats && gamma && beta && ws && M > 0 && C > 0 && C % 4 == 0 && !run_mean == !run_var, -1);
   const int rpc = BN_RPC;
   const int nchunk = (M + rpc - 1) / rpc;
   MZ_CHECK_ARG((long long)nchunk * C * (long long)sizeof(float2) <= ws_bytes, -2);
@@ -1663,7 +1663,7 @@ int mzba_bn_stats_final(const float* part, int nchunk, int rpc, int M, int C, fl
                         const float* gamma, const float* beta, float* stats, float* run_mean, float* run_var,
                         hipStream_t stream) {
   MZ_CHECK_ARG(part && stats && gamma && beta && nchunk > 0 && rpc > 0 && M > 0 && C > 0 &&
-               (long long)nchunk * rpc >= M && (long long)(nchunk - 1) * rpc < M, -1);
+               (long long)nchunk * rpc >= M && (long long)(nchunk - 1) * rpc < M && !run_mean == !run_var, -1);
   hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(64), 0, stream, (const float2*)part, nchunk, rpc, M, C, eps,
                      momentum, gamma, beta, stats, run_mean, run_var);
   MZ_LAUNCH_CHECK();
@@ -1953,7 +1953,7 @@ int mzba_conv_wgrad_segs(int dtype, const void* const* xs, const void* const* dy
 }
 
 int mzba_avgpool2_backward(int dtype, const void* dy, void* dx, int B, int H, int W, int C, hipStream_t stream) {
-  MZ_CHECK_ARG(dy && dx && B > 0 && H % 2 == 0 && W % 2 == 0, -1);
+  MZ_CHECK_ARG(dy && dx && B > 0 && H > 0 && W > 0 && C > 0 && H % 2 == 0 && W % 2 == 0, -1);
   return dispatch(dtype, [&](auto t) {
     using T = decltype(t);
     if (C % 4 == 0 && (long long)B * H * W * C < (1LL << 31))
@@ -2105,7 +2105,7 @@ int mzba_adam_dev(float* p, const float* grad, float* m, float* v, long long n, 
 
 int mzba_learner_input(int dtype, const uint8_t* states, const int64_t* past_actions, const int32_t* slots,
                        const float* lut8, void* out, int B, int L, int HW, int Cp, hipStream_t stream) {
-  MZ_CHECK_ARG(states && past_actions && slots && lut8 && out && B > 0 && L > 0 && Cp >= 2 * L, -1);
+  MZ_CHECK_ARG(states && past_actions && slots && lut8 && out && B > 0 && L > 0 && HW > 0 && Cp >= 2 * L, -1);
   return dispatch(dtype, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(learner_input_kernel<T>, dim3(grid_for((size_t)B * HW * Cp)), dim3(256), 0, stream, states,
@@ -2117,7 +2117,9 @@ int mzba_learner_input(int dtype, const uint8_t* states, const int64_t* past_act
 
 int mzba_dyn_input(int dtype, const void* h, const int64_t* future_actions, const int32_t* slots, int K, int k,
                    void* out, int B, int HW, int C, int A, int Cp, hipStream_t stream) {
-  MZ_CHECK_ARG(h && future_actions && slots && out && B > 0 && k >= 0 && k < K && Cp >= C + A, -1);
+  MZ_CHECK_ARG(h && future_actions && slots && out && B > 0 && HW > 0 && C > 0 && A >= 0 && k >= 0 && k < K &&
+                   Cp >= C + A,
+               -1);
   return dispatch(dtype, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(dyn_input_kernel<T>, dim3(grid_for((size_t)B * HW * Cp)), dim3(256), 0, stream, (const T*)h,

@@ -259,3 +259,87 @@ def test_learner_optimizer_param_groups_persist_and_lr_writes_reach_the_learner(
     opt.param_groups[0]["weight_decay"] = 0.0
     with pytest.raises(NotImplementedError):
         opt._sync_groups(Ag._learner)
+
+
+def test_learner_entry_points_reject_bad_arguments_without_gpu():
+    """Every learner entry point of csrc/learn.hip that tests/test_gpu_learner_ops.py covers checks its arguments
+    before any HIP call: otherwise valid (dummy, non-null) arguments with one violation each return the documented
+    code. Runs only where no GPU is visible, so a missing check can never launch a kernel on the dummy pointers."""
+    import ctypes
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("GPU present: a missing check would launch on dummy pointers")
+    from mzba import _lib
+    L = _lib.lib()
+    p, q = ctypes.c_void_p(4096), ctypes.c_void_p(8192)
+    eps, mom = 1e-5, 0.1
+    # BatchNorm: C % 4, scratch one byte short, empty batch, one running statistic without the other, dtype
+    assert L.mzba_bn_stats(0, p, 65, 6, eps, mom, p, p, p, p, p, p, 1 << 20, None) == -1
+    assert L.mzba_bn_stats(0, p, 0, 8, eps, mom, p, p, p, p, p, p, 1 << 20, None) == -1
+    assert L.mzba_bn_stats(0, p, 65, 8, eps, mom, p, p, p, p, None, p, 1 << 20, None) == -1
+    assert L.mzba_bn_stats(0, p, 65, 8, eps, mom, p, p, p, None, p, p, 1 << 20, None) == -1
+    assert L.mzba_bn_stats(1, p, 65, 8, eps, mom, p, p, p, p, p, p, 2 * 8 * 8 - 1, None) == -2
+    assert L.mzba_bn_stats(2, p, 65, 8, eps, mom, p, p, p, p, p, p, 1 << 20, None) == -9
+    assert L.mzba_bn_stats_final(p, 2, 64, 129, 8, eps, mom, p, p, p, p, p, None) == -1
+    assert L.mzba_bn_stats_final(p, 3, 64, 128, 8, eps, mom, p, p, p, p, p, None) == -1
+    assert L.mzba_bn_stats_final(p, 2, 64, 128, 8, eps, mom, p, p, p, p, None, None) == -1
+    assert L.mzba_bn_apply(0, p, p, None, 1, p, 65, 6, None) == -1
+    assert L.mzba_bn_apply(1, p, p, None, 1, None, 65, 8, None) == -1
+    assert L.mzba_bn_backward(0, p, p, p, p, 65, 6, p, p, p, p, 1 << 20, None) == -1
+    assert L.mzba_bn_backward(1, p, None, p, p, 65, 8, p, p, p, p, 2 * 8 * 8 + 12 * 8 - 1, None) == -2
+    assert L.mzba_bn_backward_final(0, p, p, p, p, 2, 65, 6, p, p, p, p, 1 << 20, None) == -1
+    assert L.mzba_bn_backward_final(1, p, p, p, p, 2, 65, 8, p, p, p, p, 12 * 8 - 1, None) == -2
+    assert L.mzba_bn_backward_coef(p, 0, 65, 8, p, p, p, p, None) == -1
+    assert L.mzba_bn_backward_coef(p, 2, 65, 8, p, p, p, None, None) == -1
+    assert L.mzba_bn_backward_apply(0, p, p, p, p, p, 65, 6, None) == -1
+    # avg-pool backward: odd or empty extents; axpy; the min-max scale
+    for H, W, C in ((3, 4, 8), (4, 5, 8), (0, 4, 8), (4, 0, 8), (4, 4, 0), (-2, 4, 8)):
+        assert L.mzba_avgpool2_backward(0, p, q, 3, H, W, C, None) == -1, (H, W, C)
+    assert L.mzba_avgpool2_backward(1, p, q, 0, 4, 4, 8, None) == -1
+    assert L.mzba_axpy(0, p, q, -1, None) == -1
+    assert L.mzba_axpy(1, p, None, 4, None) == -1
+    assert L.mzba_scale_forward(0, p, q, p, p, 5, 0, 4, None) == -1
+    assert L.mzba_scale_forward(1, p, q, p, p, 5, 20, 0, None) == -1
+    assert L.mzba_scale_backward(0, p, p, p, p, q, 5, 0, 0, None) == -1
+    assert L.mzba_scale_backward(1, p, p, p, None, q, 5, 80, 1, None) == -1
+    # Linear heads: at most 16 outputs, scratch one byte short
+    assert L.mzba_linear_forward(0, p, p, p, q, 4, 100, 17, None) == -1
+    assert L.mzba_linear_forward(1, p, p, p, q, 4, 100, 0, None) == -1
+    assert L.mzba_linear_backward(0, p, p, p, q, 0, p, p, 64, 100, 17, p, 1 << 20, None) == -1
+    need = L.mzba_linear_ws_bytes(64, 100, 3)
+    assert need == 16 * (3 * 100 + 3) * 4
+    assert L.mzba_linear_backward(1, p, p, p, None, 0, p, p, 64, 100, 3, p, need - 1, None) == -2
+    # loss: 2 <= ns <= 16, 1 <= na <= 16, scratch one byte short
+    lo, hi = ctypes.c_float(-5.0), ctypes.c_float(5.0)
+    for ns, na in ((17, 3), (11, 17), (1, 3), (11, 0)):
+        assert L.mzba_learner_loss(p, p, p, p, p, p, None, 4, 5, ns, na, lo, hi, q, q, q, q, None) == -1, (ns, na)
+        assert L.mzba_learner_loss_ws(p, p, p, p, p, p, None, 4, 5, ns, na, lo, hi, q, q, q, q, p, 1 << 20,
+                                      None) == -1, (ns, na)
+    assert L.mzba_learner_loss_ws_bytes(4, 5) == 3 * 4 * 5 * 8
+    assert L.mzba_learner_loss_ws(p, p, p, p, p, p, p, 4, 5, 11, 3, lo, hi, q, q, q, q, p, 3 * 4 * 5 * 8 - 1, None) == -2
+    # Adam
+    sc = [ctypes.c_float(v) for v in (-1e-3, 0.1, 0.999, 1e-3, 1.0, 1e-8, 1e-4)]
+    assert L.mzba_adam(p, p, p, p, -1, *sc, None) == -1
+    assert L.mzba_adam(p, p, None, p, 8, *sc, None) == -1
+    assert L.mzba_adam_dev(p, p, p, p, -1, p, None) == -1
+    assert L.mzba_adam_dev(p, p, p, p, 8, None, None) == -1
+    # input builders: room for the 2 L planes, an image, an unroll step below K, room for h and the action planes
+    assert L.mzba_learner_input(0, p, p, p, p, q, 5, 4, 20, 7, None) == -1
+    assert L.mzba_learner_input(1, p, p, p, p, q, 5, 4, 0, 8, None) == -1
+    assert L.mzba_learner_input(0, p, p, None, p, q, 5, 4, 20, 8, None) == -1
+    assert L.mzba_dyn_input(0, p, p, p, 5, 5, q, 5, 20, 32, 3, 40, None) == -1
+    assert L.mzba_dyn_input(1, p, p, p, 5, -1, q, 5, 20, 32, 3, 40, None) == -1
+    assert L.mzba_dyn_input(0, p, p, p, 5, 0, q, 5, 0, 32, 3, 40, None) == -1
+    assert L.mzba_dyn_input(1, p, p, p, 5, 0, q, 5, 20, 32, 3, 34, None) == -1
+    # batched weight pack: job count, output alignment, pad % 8, layout, the layouts' shape rules, the flip rule
+    w, o = (ctypes.c_void_p * 1)(4096), (ctypes.c_void_p * 1)(8192)
+
+    def pack(*prm, out=o, njobs=1):
+        return L.mzba_conv_pack_bf16_multi(w, out, (ctypes.c_int * 8)(*prm), njobs, None)
+    assert pack(32, 9, 32, 32, 32, 0, 1, 8, njobs=0) == -1
+    assert pack(32, 9, 32, 32, 32, 0, 1, 8, out=(ctypes.c_void_p * 1)(8200)) == -1
+    assert pack(32, 9, 32, 32, 32, 0, 1, 4) == -1
+    assert pack(32, 9, 32, 32, 32, 0, 3, 8) == -1
+    assert pack(48, 9, 32, 48, 32, 0, 1, 8) == -2
+    assert pack(16, 1, 64, 16, 64, 0, 2, 8) == -3
+    assert pack(32, 9, 64, 64, 64, 1, 1, 8) == -4
