@@ -274,6 +274,39 @@ int mzba_replay_write(const uint8_t* action, const float* reward, const uint8_t*
 int mzba_replay_states(const uint8_t* states, const int32_t* slots, int n, const float* lut8, float* out, int hist,
                        int HW, hipStream_t stream);
 
+/* ===================== prioritized replay (MuZero, Appendix G; csrc/replay_prio.hip)
+ * q f32[cap], 16-byte aligned, in slot space: q[slot] = p^alpha for a live window, exactly 0 for a slot that
+ * holds no window (the owner zeroes q when it empties the ring), so the sampler needs neither the ring's start
+ * nor its length.
+ * priority_init: after mzba_replay_write(…, cap, head, …) of n_windows windows, over the same slots
+ *   (head + j) % cap, j in [max(0, n_windows - cap), n_windows): p = |values[slot][0] - targets[slot][0]| + eps
+ *   (searched root value against the n-step target at the window's root step), q[slot] = p^alpha.
+ * priority_update: q[slots[j]] = (td[j] + eps)^alpha, j < n; slots are ring rows (a sample's output); a slot
+ *   outside [0, cap) is skipped, never written.
+ *   Duplicate slots in one batch must carry equal td (any writer may win). The caller guarantees that no ingest
+ *   ran between the sample that gave `slots` and this call, or a reused slot would get its old window's priority;
+ *   the stream order of a training stage (sample, minibatch, update) gives that.
+ * p^alpha is evaluated in double and rounded once to f32 (alpha == 1: p itself).
+ * sample: n stratified inverse-CDF draws. With C the inclusive prefix sum of q over slots 0..cap-1 and S =
+ *   C[cap-1], sample j takes u_j in [0, 1) = u_in[j], or (u_in NULL) the Philox uniform of counter (j, stream 4,
+ *   step, 0) under `seed` with step = step_dev ? step_dev[0] : step (device u32[1]: a captured graph draws afresh
+ *   on every replay), the target t_j = ((j + u_j) / n) S in f64, and returns the slot i with C[i-1] <= t_j < C[i].
+ *   Sums are f64 in one fixed order (block sums, a scan of them, a scan inside the block; no atomics): the same
+ *   inputs give the same slots on every run. A slot with q == 0 is never returned; where rounding puts t_j at or
+ *   beyond S the last slot with q > 0 is. prob[j] = q_i / S; weight[j] = (n_live prob[j])^-beta over the largest
+ *   such value of the batch, in (0, 1] (n_live, the number of stored windows, cancels up to rounding; beta == 0
+ *   gives exactly 1). cap, n <= 2^20. n_live <= 0 (an empty buffer, S == 0) is an argument error (-3), not a
+ *   launch. ws >= mzba_replay_sample_ws_bytes(cap, n) bytes, 16-byte aligned. Four launches, no host
+ *   synchronisation. */
+int mzba_replay_priority_init(float* q, const float* values, const float* targets, int cap, int head, int n_windows,
+                              int K, float alpha, float eps, hipStream_t stream);
+int mzba_replay_priority_update(float* q, const int32_t* slots, const float* td, int n, int cap, float alpha,
+                                float eps, hipStream_t stream);
+long long mzba_replay_sample_ws_bytes(int cap, int n);
+int mzba_replay_sample(const float* q, int cap, int n, float beta, int n_live, uint64_t seed, uint32_t step,
+                       const uint32_t* step_dev, const float* u_in, int32_t* slots, float* prob, float* weight,
+                       void* ws, long long ws_bytes, hipStream_t stream);
+
 /* kernel choice for experiments/tests: 0 by batch (default), 1 four-env 8-wave kernel, 2 eight-env
  * kernel, 3 four-env 4-wave kernel */
 int mzba_tower_set_variant(int v);
@@ -581,6 +614,15 @@ int mzba_learner_loss_ws(const float* logit_r, const float* logit_v, const float
                          const float* targets, const float* counts, const int32_t* slots, int B, int K, int ns, int na,
                          float smin, float smax, float* dlogit_r, float* dlogit_v, float* dlogit_p, float* loss,
                          void* ws, long long ws_bytes, hipStream_t stream);
+/* mzba_learner_loss_ws for prioritized replay: row (b, k)'s three KL terms and its three logit-gradient rows are
+ * multiplied by weights[b] (f32[B], the sampler's importance weights) before the same reduction with the same
+ * 1 / (B K); weights NULL, or all 1.0f (an exact multiply), give mzba_learner_loss_ws's outputs bit for bit.
+ * td (f32[B], NULL: not written): td[b] = |inverted_softmax_expectation(logit_v[0][b]) - targets[slots[b]][0]|
+ * (mzba_support_decode's arithmetic): the window's new priority, from the learner's own value prediction. */
+int mzba_learner_loss_w(const float* logit_r, const float* logit_v, const float* logit_p, const float* rewards,
+                        const float* targets, const float* counts, const int32_t* slots, int B, int K, int ns, int na,
+                        float smin, float smax, float* dlogit_r, float* dlogit_v, float* dlogit_p, float* loss,
+                        void* ws, long long ws_bytes, const float* weights, float* td, hipStream_t stream);
 /* Adam with L2 weight decay, torch single-tensor order: g = grad + wd*p; m += (1-b1)(g - m);
  * v = v*b2 + (1-b2)*g*g; p += (-step_size*m) / (sqrt(v)/bc2_sqrt + eps). Host computes
  * neg_step = -lr/(1-b1^t), bc2_sqrt = sqrt(1-b2^t) in double (python float semantics). */

@@ -1466,13 +1466,20 @@ __global__ __launch_bounds__(LOSS_T) void loss_kernel(const float* __restrict__ 
 // a thread per row r computes its three KL terms (gradients written as loss_kernel) and stores them to
 // ws[j][r]; loss_reduce_kernel then folds them exactly as loss_kernel's threads did — thread t adds rows t,
 // t + LOSS_T, ... in order into its double accumulators, then the same tree — so the loss is bit-identical
+//
+// PRIO (mzba_learner_loss_w, prioritized replay): row (b, k)'s three KL terms and its three gradient rows are
+// multiplied by weights[b] (NULL: by nothing) before the fold — by 1.0f that is exact, so all-ones weights give
+// the unweighted bits — and the k = 0 row leaves td[b] = |decode_support(logit_v[0][b]) - targets[slot][0]| (NULL:
+// not written), the window's new priority (Ape-X: from the learner's own value prediction).
+template <bool PRIO>
 __global__ __launch_bounds__(256) void loss_rows_kernel(const float* __restrict__ lr, const float* __restrict__ lv,
                                                         const float* __restrict__ lp, const float* __restrict__ rewards,
                                                         const float* __restrict__ targets,
                                                         const float* __restrict__ counts, const int32_t* slots, int B,
                                                         int K, int ns, int na, float smin, float smax,
                                                         float* __restrict__ dlr, float* __restrict__ dlv,
-                                                        float* __restrict__ dlp, double* __restrict__ ws) {
+                                                        float* __restrict__ dlp, double* __restrict__ ws,
+                                                        const float* __restrict__ weights, float* __restrict__ td) {
   const float scale = (1.f / (float)K) / (float)(B * K);
   const int r = blockIdx.x * blockDim.x + threadIdx.x, BK = B * K;
   if (r >= BK) return;
@@ -1480,19 +1487,25 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(const float* __restrict_
   const size_t src = slots ? (size_t)slots[b] : (size_t)b;
   float t[16], z[16], dz[16];
   const size_t o1 = ((size_t)k * B + b) * ns, o3 = ((size_t)k * B + b) * na;
+  const bool wt = PRIO && weights;
+  const float w = wt ? weights[b] : 1.f;
   two_hot(rewards[src * K + k], smin, smax, ns, t);
   for (int i = 0; i < ns; ++i) z[i] = lr[o1 + i];
-  ws[r] = kl_row(z, t, ns, scale, dz);
-  for (int i = 0; i < ns; ++i) dlr[o1 + i] = dz[i];
+  double kl = kl_row(z, t, ns, scale, dz);
+  ws[r] = wt ? kl * (double)w : kl;
+  for (int i = 0; i < ns; ++i) dlr[o1 + i] = wt ? dz[i] * w : dz[i];
   two_hot(targets[src * K + k], smin, smax, ns, t);
   for (int i = 0; i < ns; ++i) z[i] = lv[o1 + i];
-  ws[BK + r] = kl_row(z, t, ns, scale, dz);
-  for (int i = 0; i < ns; ++i) dlv[o1 + i] = dz[i];
+  if (PRIO && td && k == 0) td[b] = fabsf(decode_support(z, ns, smin, smax) - targets[src * K]);
+  kl = kl_row(z, t, ns, scale, dz);
+  ws[BK + r] = wt ? kl * (double)w : kl;
+  for (int i = 0; i < ns; ++i) dlv[o1 + i] = wt ? dz[i] * w : dz[i];
   float cs = 0.f;
   for (int i = 0; i < na; ++i) cs += counts[(src * K + k) * na + i];
   for (int i = 0; i < na; ++i) { t[i] = counts[(src * K + k) * na + i] / cs; z[i] = lp[o3 + i]; }
-  ws[2 * BK + r] = kl_row(z, t, na, scale, dz);
-  for (int i = 0; i < na; ++i) dlp[o3 + i] = dz[i];
+  kl = kl_row(z, t, na, scale, dz);
+  ws[2 * BK + r] = wt ? kl * (double)w : kl;
+  for (int i = 0; i < na; ++i) dlp[o3 + i] = wt ? dz[i] * w : dz[i];
 }
 
 __global__ __launch_bounds__(LOSS_T) void loss_reduce_kernel(const double* __restrict__ ws, int B, int K,
@@ -2064,8 +2077,26 @@ int mzba_learner_loss_ws(const float* logit_r, const float* logit_v, const float
                -1);
   MZ_CHECK_ARG(mzba_learner_loss_ws_bytes(B, K) <= ws_bytes && (long long)B * K < (1LL << 28), -2);
   const int BK = B * K;
-  hipLaunchKernelGGL(loss_rows_kernel, dim3((BK + 255) / 256), dim3(256), 0, stream, logit_r, logit_v, logit_p, rewards,
-                     targets, counts, slots, B, K, ns, na, smin, smax, dlogit_r, dlogit_v, dlogit_p, (double*)ws);
+  hipLaunchKernelGGL(loss_rows_kernel<false>, dim3((BK + 255) / 256), dim3(256), 0, stream, logit_r, logit_v, logit_p,
+                     rewards, targets, counts, slots, B, K, ns, na, smin, smax, dlogit_r, dlogit_v, dlogit_p, (double*)ws,
+                     (const float*)nullptr, (float*)nullptr);
+  hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(LOSS_T), 0, stream, (const double*)ws, B, K, loss);
+  MZ_LAUNCH_CHECK();
+  return 0;
+}
+
+int mzba_learner_loss_w(const float* logit_r, const float* logit_v, const float* logit_p, const float* rewards,
+                        const float* targets, const float* counts, const int32_t* slots, int B, int K, int ns, int na,
+                        float smin, float smax, float* dlogit_r, float* dlogit_v, float* dlogit_p, float* loss,
+                        void* ws, long long ws_bytes, const float* weights, float* td, hipStream_t stream) {
+  MZ_CHECK_ARG(logit_r && logit_v && logit_p && rewards && targets && counts && dlogit_r && dlogit_v && dlogit_p &&
+                   loss && ws && B > 0 && K > 0 && ns >= 2 && ns <= 16 && na > 0 && na <= 16,
+               -1);
+  MZ_CHECK_ARG(mzba_learner_loss_ws_bytes(B, K) <= ws_bytes && (long long)B * K < (1LL << 28), -2);
+  const int BK = B * K;
+  hipLaunchKernelGGL(loss_rows_kernel<true>, dim3((BK + 255) / 256), dim3(256), 0, stream, logit_r, logit_v, logit_p,
+                     rewards, targets, counts, slots, B, K, ns, na, smin, smax, dlogit_r, dlogit_v, dlogit_p, (double*)ws,
+                     weights, td);
   hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(LOSS_T), 0, stream, (const double*)ws, B, K, loss);
   MZ_LAUNCH_CHECK();
   return 0;

@@ -17,6 +17,7 @@ P = ctypes.c_void_p
 I = ctypes.c_int
 LL = ctypes.c_longlong
 U64 = ctypes.c_uint64
+U32 = ctypes.c_uint32
 F = ctypes.c_float
 D = ctypes.c_double
 
@@ -64,6 +65,11 @@ SIGNATURES = {
     "mzba_replay_plan": [P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P],
     "mzba_replay_write": [P, P, P, P, P, P, P, I, I, I, P, P, P, I, P, P, P, P, P, P, P, P, I, I, I, I, P, P],
     "mzba_replay_states": [P, P, I, P, P, I, I, P],
+    # prioritized replay (replay_prio.hip)
+    "mzba_replay_priority_init": [P, P, P, I, I, I, I, F, F, P],
+    "mzba_replay_priority_update": [P, P, P, I, I, F, F, P],
+    "mzba_replay_sample_ws_bytes": [I, I],
+    "mzba_replay_sample": [P, I, I, F, I, U64, U32, P, P, P, P, P, P, LL, P],
     "mzba_conv_band": [P, P, P, P, P, I, I, I, I, I, I, P],
     "mzba_conv_band_res_supported": [I, I, I],
     "mzba_conv_band_res": [P, P, P, P, P, P, I, I, I, I, P],
@@ -115,6 +121,7 @@ SIGNATURES = {
     "mzba_learner_loss": [P, P, P, P, P, P, P, I, I, I, I, F, F, P, P, P, P, P],
     "mzba_learner_loss_ws_bytes": [I, I],
     "mzba_learner_loss_ws": [P, P, P, P, P, P, P, I, I, I, I, F, F, P, P, P, P, P, LL, P],
+    "mzba_learner_loss_w": [P, P, P, P, P, P, P, I, I, I, I, F, F, P, P, P, P, P, LL, P, P, P],
     "mzba_adam": [P, P, P, P, LL, F, F, F, F, F, F, F, P],
     "mzba_adam_dev": [P, P, P, P, LL, P, P],
     "mzba_learner_input": [I, P, P, P, P, P, I, I, I, I, P],
@@ -144,7 +151,7 @@ class TowerExt(ctypes.Structure):
 
 # entry points that return something other than a status code
 RESTYPES = {"mzba_tower_ws_bytes": LL, "mzba_tower_plan": I, "mzba_conv_lat_get_variant": I, "mzba_conv_wgrad_ws_bytes": LL,
-            "mzba_linear_ws_bytes": LL, "mzba_learner_loss_ws_bytes": LL}
+            "mzba_linear_ws_bytes": LL, "mzba_learner_loss_ws_bytes": LL, "mzba_replay_sample_ws_bytes": LL}
 
 
 def lib():

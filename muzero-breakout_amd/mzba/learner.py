@@ -176,6 +176,9 @@ class Learner:
         self._owed = {}  # the values (_Val) that still owe their BN apply, in creation order (an ordered set)
         self._pending = None  # deferred latent weight gradients: conv -> [(x, dY)] in backward order
         self._graph = None        # captured minibatch (capture()), replayed by train_minibatch
+        self._g_prio = False      # the captured graph is a whole prioritized step (capture(prioritized=True))
+        self.per_step = 0         # prioritized steps taken: the sampler's Philox step
+        self.last_td = self.last_slots = self.last_weights = None
         self._capturing = False
         if dtype not in ("f32", "bf16"):
             raise ValueError("dtype must be 'f32' or 'bf16'")
@@ -809,12 +812,19 @@ class Learner:
         return gh
 
     # -- one minibatch ------------------------------------------------------------------------------
-    def train_minibatch(self, ring, slots):
+    def train_minibatch(self, ring, slots, weights=None):
         """One `_training_stage` iteration on replay windows `slots` (i32 ring rows) of `ring`
         (a DeviceReplayBuffer, or any object with the same `_ring` dict). Returns the device
         loss vector (total, reward, value, policy). Replays the captured graph (capture()) when
-        it was captured for this ring and minibatch size."""
-        if self._graph is not None and ring is self._g_ring and slots.numel() == self._g_slots.numel():
+        it was captured for this ring and minibatch size.
+
+        `weights` (device f32[B], prioritized replay's importance weights) scale each window's loss terms
+        and gradients (mzba_learner_loss_w; always eager) and leave `self.last_td`, device f32[B]:
+        |decoded value prediction at the root - the window's n-step target|, the windows' new priorities."""
+        if weights is not None:
+            return self._minibatch(ring, slots, weights)
+        if self._graph is not None and not self._g_prio and ring is self._g_ring and \
+                slots.numel() == self._g_slots.numel():
             self._g_slots.copy_(slots.to(device=self.device, dtype=torch.int32))
             self.step_count += 1
             self._adam_sc.copy_(torch.tensor(self._adam_scalars(self.step_count), dtype=torch.float32))
@@ -828,48 +838,93 @@ class Learner:
         b1, b2 = BETAS
         return [-(self.lr / (1 - b1 ** t)), 1 - b1, b2, 1 - b2, (1 - b2 ** t) ** 0.5, ADAM_EPS, WEIGHT_DECAY]
 
-    def capture(self, ring, B):
+    def capture(self, ring, B, prioritized=False, seed=0):
         """Capture one minibatch of B windows of `ring` as a HIP graph (torch.cuda.graph: every
         activation in the graph's private pool; slots read from a static buffer, Adam's bias
         corrections from a device scalar block), so a minibatch is one graph launch from the
         host. Call after at least one eager minibatch of the same size (weight packs and scratch
-        buffers allocated). Replays are launch-for-launch the eager minibatch (bit-identical)."""
+        buffers allocated). Replays are launch-for-launch the eager minibatch (bit-identical).
+
+        prioritized=True (a DeviceReplayBuffer(prioritized=True)) captures a whole prioritized step:
+        ring.sample -> the weighted minibatch -> ring.update_priorities -> the device step counter + 1
+        (the sampler's Philox step, starting at self.per_step); prioritized_step() replays it."""
         if self.streams == 2 and self._side_stream is None:
             # the side stream must exist (default priority, created by an eager minibatch) before
             # capture: no stream is created or re-prioritised inside torch.cuda.graph (DESIGN.md §10)
             raise RuntimeError("Learner.capture: run one eager minibatch of this size first")
         self._graph = None
+        self._g_prio, self._g_seed = bool(prioritized), int(seed)
         self._g_slots = torch.zeros(B, dtype=torch.int32, device=self.device)
         self._adam_sc = torch.zeros(7, dtype=torch.float32, device=self.device)
+        if prioritized:
+            # the sampler's step on the device, advanced inside the graph; _g_step_host is what it holds
+            self._g_step = torch.full((1,), self.per_step, dtype=torch.int32, device=self.device)
+            self._g_step_host = self.per_step
+            ring._sample_workspace(B)  # the ring's own scratch: not from the graph's private pool
         nbt0, step0 = dict(self.nbt), self.step_count
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph()
         self._capturing = True
         try:
             with torch.cuda.graph(g):
-                loss = self._minibatch(ring, self._g_slots)
+                if prioritized:
+                    loss = self._prioritized_body(ring, B, seed, self._g_step)
+                    self._g_step.add_(1)
+                else:
+                    loss = self._minibatch(ring, self._g_slots)
         finally:
             self._capturing = False
         # capture records launches without running them: undo its host-side counters
         self._nbt_step = {k: self.nbt[k] - nbt0[k] for k in self.nbt}
         self.nbt, self.step_count = nbt0, step0
         self._graph, self._g_ring, self._g_loss = g, ring, loss
+        if prioritized:
+            self._g_last = (self.last_slots, self.last_weights, self.last_td)
 
-    def _minibatch(self, ring, slots):
+    def prioritized_step(self, ring, B, seed=0):
+        """One prioritized minibatch on `ring` (a DeviceReplayBuffer(prioritized=True)): B windows sampled in
+        proportion to their priorities, trained with their importance weights, their priorities rewritten from
+        the value error the step has just seen; no host round trip. Replays capture(ring, B, prioritized=True,
+        seed) when that was captured. Leaves last_slots / last_weights / last_td; returns the device losses."""
+        if self._graph is not None and self._g_prio and ring is self._g_ring and B == self._g_slots.numel() and \
+                int(seed) == self._g_seed:
+            self.step_count += 1
+            self._adam_sc.copy_(torch.tensor(self._adam_scalars(self.step_count), dtype=torch.float32))
+            if self._g_step_host != self.per_step:  # eager steps were taken since the last replay
+                self._g_step.fill_(self.per_step)
+            self._graph.replay()
+            for k, d in self._nbt_step.items():
+                self.nbt[k] += d
+            self.per_step += 1
+            self._g_step_host = self.per_step
+            self.last_slots, self.last_weights, self.last_td = self._g_last
+            return self._g_loss
+        loss = self._prioritized_body(ring, B, seed, None)
+        self.per_step += 1
+        return loss
+
+    def _prioritized_body(self, ring, B, seed, step_dev):
+        slots, weights, _ = ring.sample(B, self.per_step, seed=seed, step_dev=step_dev)
+        loss = self._minibatch(ring, slots, weights)
+        ring.update_priorities(slots, self.last_td)
+        self.last_slots, self.last_weights = slots, weights
+        return loss
+
+    def _minibatch(self, ring, slots, weights=None):
         """One minibatch with conv_lat set to this learner's tile rows (variant 2 = 5-row tiles only, 3 = 3-row
         tiles on the two-workgroups-per-CU instance, 0 = auto), restored afterwards; a captured graph keeps the
         shapes it recorded."""
         prev = L.lib().mzba_conv_lat_get_variant()
         want = {5: 2, 3: 3}.get(self.lat_rows, 0)
         if prev == want:
-            return self._minibatch_body(ring, slots)
+            return self._minibatch_body(ring, slots, weights)
         L.call("mzba_conv_lat_set_variant", want)
         try:
-            return self._minibatch_body(ring, slots)
+            return self._minibatch_body(ring, slots, weights)
         finally:
             L.call("mzba_conv_lat_set_variant", prev)
 
-    def _minibatch_body(self, ring, slots):
+    def _minibatch_body(self, ring, slots, weights=None):
         g = ring._ring
         slots = slots.to(device=self.device, dtype=torch.int32).contiguous()
         B, K, Lh = slots.numel(), self.K, self.hist
@@ -912,9 +967,17 @@ class Learner:
         dlr, dlv, dlp = torch.empty_like(lr_all), torch.empty_like(lv_all), torch.empty_like(lp_all)
         loss = torch.empty(4, device=self.device)
         lws = self._scratch("loss", L.lib().mzba_learner_loss_ws_bytes(B, K))
-        L.call("mzba_learner_loss_ws", L.ptr(lr_all), L.ptr(lv_all), L.ptr(lp_all), L.ptr(g["rewards"]),
-               L.ptr(g["targets"]), L.ptr(g["counts"]), L.ptr(slots), B, K, self.ns, self.na, self.smin, self.smax,
-               L.ptr(dlr), L.ptr(dlv), L.ptr(dlp), L.ptr(loss), L.ptr(lws), lws.numel(), s)
+        largs = (L.ptr(lr_all), L.ptr(lv_all), L.ptr(lp_all), L.ptr(g["rewards"]), L.ptr(g["targets"]),
+                 L.ptr(g["counts"]), L.ptr(slots), B, K, self.ns, self.na, self.smin, self.smax, L.ptr(dlr), L.ptr(dlv),
+                 L.ptr(dlp), L.ptr(loss), L.ptr(lws), lws.numel())
+        if weights is None:
+            L.call("mzba_learner_loss_ws", *largs, s)
+        else:
+            weights = weights.to(device=self.device, dtype=torch.float32).contiguous()
+            if weights.numel() != B:
+                raise ValueError("weights must hold one value per window")
+            self.last_td = torch.empty(B, dtype=torch.float32, device=self.device)
+            L.call("mzba_learner_loss_w", *largs, L.ptr(weights), L.ptr(self.last_td), s)
         self.last_logits = (lr_all, lv_all, lp_all)
         # ---- backward
         # prediction k: heads -> res blocks -> d h_k (prediction part); independent of the dynamics
@@ -1038,9 +1101,15 @@ class Learner:
         fl += self.K * sum(3 * 2.0 * B * hw * cin * o for cin, o in lin)
         return fl
 
-    def training_stage(self, ring, num_batches, minibatch_size, generator=None):
+    def training_stage(self, ring, num_batches, minibatch_size, generator=None, prioritized=False, seed=0):
         """`_training_stage` loop (train_torch.py:373-407): randperm over the buffer, num_batches
-        minibatches; returns the per-minibatch losses (host floats)."""
+        minibatches; returns the per-minibatch losses (host floats).
+
+        prioritized=True: num_batches prioritized_step()s instead (sample, train, update priorities on the
+        device; the only host read is that of the losses at the end)."""
+        if prioritized:
+            losses = [self.prioritized_step(ring, minibatch_size, seed).clone() for _ in range(num_batches)]
+            return [float(x[0]) for x in losses]
         n = len(ring)
         perm = torch.randperm(n, generator=generator)
         losses = []

@@ -6,6 +6,10 @@ loop's sink (`ingest_records`) or from host `ObservationTrajectory` objects
 (`save_observation_trajectory`, same arithmetic). Storage is a FIFO ring of `max_length`
 fixed-size rows in HBM (frames as u8 gray codes, 10 KB per window at 16x20); the getters
 return device tensors with the reference's dtypes and shapes.
+
+`prioritized=True` adds MuZero's prioritized replay (Appendix G; csrc/replay_prio.hip): a
+priority array beside the ring, set at ingest from |searched value - n-step target|, a device sampler
+(`sample`) and the learner's write-back (`update_priorities`). Off by default; nothing else changes.
 """
 import numpy as np
 import torch
@@ -17,7 +21,8 @@ from .env import gray_lut
 class DeviceReplayBuffer:
     """ReplayBuffer(seq_len, K, max_length, discount, num_rewards_to_sum) (replay_buffer.py:76-92)."""
 
-    def __init__(self, seq_len, K, max_length, discount, num_rewards_to_sum, height=16, width=20, device="cuda"):
+    def __init__(self, seq_len, K, max_length, discount, num_rewards_to_sum, height=16, width=20, device="cuda",
+                 prioritized=False, alpha=1.0, beta=1.0, prio_eps=1e-3):
         L.require_gpu()
         self.hist_seq_len, self.K, self.max_length = seq_len, K, max_length
         self.discount, self.num_rewards_to_sum = discount, num_rewards_to_sum
@@ -38,6 +43,12 @@ class DeviceReplayBuffer:
         self.start = 0      # ring slot of the oldest window
         self.length = 0     # windows stored (replay_buffer.py:87)
         self._dpow = {}
+        # prioritized replay: q[slot] = p^alpha of a live window, exactly 0 for a slot that holds none (slot space,
+        # so the sampler needs neither start nor length); kept outside _ring, which other ring holders imitate
+        self.prioritized = bool(prioritized)
+        self.alpha, self.beta, self.prio_eps = float(alpha), float(beta), float(prio_eps)
+        self._q = torch.zeros(cap, dtype=torch.float32, device=dev) if self.prioritized else None
+        self._sample_ws = {}
 
     def __len__(self):
         return self.length
@@ -79,6 +90,8 @@ class DeviceReplayBuffer:
                L.ptr(g["future_actions"]), L.ptr(g["states"]), L.ptr(g["rewards"]), L.ptr(g["counts"]),
                L.ptr(g["values"]), L.ptr(g["targets"]), L.ptr(g["reward_sum"]), cap, head, self.K,
                self.hist_seq_len, L.ptr(self._powers(T)), L.stream())
+        if self.prioritized:
+            self._init_priorities(head, n)
         total = self.length + n
         self.length = min(total, cap)
         self.start = (self.start + total - self.length) % cap
@@ -159,13 +172,78 @@ class DeviceReplayBuffer:
 
     def empty_buffer(self):
         self.start = self.length = 0
+        if self.prioritized:
+            self._q.zero_()
+
+    # -- prioritized replay (csrc/replay_prio.hip) --------------------------------------------------
+    def _need_prio(self):
+        if not self.prioritized:
+            raise RuntimeError("this DeviceReplayBuffer was built with prioritized=False")
+
+    def _init_priorities(self, head, n):
+        """The ingest rule for the n windows written from slot `head` on (the newest max_length of them):
+        q = (|values[slot][0] - targets[slot][0]| + prio_eps) ** alpha."""
+        g = self._ring
+        L.call("mzba_replay_priority_init", L.ptr(self._q), L.ptr(g["values"]), L.ptr(g["targets"]), self.max_length,
+               head, n, self.K, self.alpha, self.prio_eps, L.stream())
+
+    def _sample_workspace(self, n):
+        """The sampler's scratch for n samples, kept per n (allocate it before a graph capture that samples)."""
+        ws = self._sample_ws.get(n)
+        if ws is None:
+            nbytes = L.lib().mzba_replay_sample_ws_bytes(self.max_length, n)
+            ws = self._sample_ws[n] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def sample(self, n, step, seed=0, u=None, step_dev=None):
+        """n windows drawn in proportion to their priorities (stratified: sample j from the j-th n-th of the
+        mass), on the device with no host round trip -> (slots i32[n] ring rows, weights f32[n] =
+        (len * P) ** -beta over the batch's largest, probs f32[n]). The draws are Philox (j, stream 4, step, 0)
+        under `seed`; `step_dev` (device i32/u32 [1]) overrides `step`, so a captured graph draws afresh on every
+        replay; `u` (device f32[n] in [0, 1)) replaces the draws. len(self) is read when the call is recorded: it
+        cancels in the normalised weights up to rounding."""
+        self._need_prio()
+        if self.length == 0:
+            raise ValueError("sample from an empty replay buffer")
+        n = int(n)
+        dev = self.device
+        slots = torch.empty(n, dtype=torch.int32, device=dev)
+        probs = torch.empty(n, dtype=torch.float32, device=dev)
+        weights = torch.empty(n, dtype=torch.float32, device=dev)
+        if u is not None:
+            u = u.to(device=dev, dtype=torch.float32).contiguous()
+            if u.numel() != n:
+                raise ValueError("u must hold one draw per sample")
+        if step_dev is not None and (step_dev.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not step_dev.is_cuda):
+            raise ValueError("step_dev must be a device int32 / uint32 tensor")
+        ws = self._sample_workspace(n)
+        L.call("mzba_replay_sample", L.ptr(self._q), self.max_length, n, self.beta, self.length, int(seed),
+               int(step) & 0xFFFFFFFF, L.ptr(step_dev), L.ptr(u), L.ptr(slots), L.ptr(probs), L.ptr(weights), L.ptr(ws),
+               ws.numel(), L.stream())
+        return slots, weights, probs
+
+    def update_priorities(self, slots, td):
+        """q[slots[j]] = (td[j] + prio_eps) ** alpha (td: the learner's last_td for the windows `slots` of a
+        `sample`). No ingest may run between the sample and this call; duplicates must carry equal td."""
+        self._need_prio()
+        if slots.dtype != torch.int32 or td.dtype != torch.float32 or slots.numel() != td.numel():
+            raise ValueError("update_priorities takes i32 slots and f32 td of one length")
+        slots, td = slots.contiguous(), td.contiguous()  # held until the launch is made
+        L.call("mzba_replay_priority_update", L.ptr(self._q), L.ptr(slots), L.ptr(td), slots.numel(), self.max_length,
+               self.alpha, self.prio_eps, L.stream())
+
+    def priorities(self):
+        """q = p ** alpha of the stored windows, oldest first (f32 device tensor)."""
+        self._need_prio()
+        idx = torch.arange(self.length, device=self.device)
+        return self._q[(idx + self.start) % self.max_length]
 
     # -- the reference's list layout (checkpoint replay_buffer, train_torch.py:624-635) ----
     def to_reference_lists(self):
         idx = torch.arange(self.length, device=self.device)
         cpu = lambda t: list(t.cpu().unbind(0)) if self.length else []  # noqa: E731
         sl = self._slots(idx) if self.length else idx
-        return {
+        d = {
             "past_actions_buffer": cpu(self._ring["past_actions"][sl]),
             "future_actions_buffer": cpu(self._ring["future_actions"][sl]),
             "state_buffer": cpu(self.get_batched_states(idx)) if self.length else [],
@@ -177,6 +255,9 @@ class DeviceReplayBuffer:
             "max_length": self.max_length,
             "bootstrapped_values": cpu(self._ring["targets"][sl]),
         }
+        if self.prioritized:  # beside the reference's keys, which stay as they are
+            d["priorities"] = self.priorities().cpu()
+        return d
 
     def load_reference_lists(self, d):
         """Replace the contents with a reference replay_buffer dict (oldest first)."""
@@ -204,3 +285,8 @@ class DeviceReplayBuffer:
         put("targets", d["bootstrapped_values"][:n], torch.float32)
         g["reward_sum"][:n].copy_(torch.tensor(np.asarray(d["reward_sums"][:n], np.float32)).to(dev))
         self.start, self.length = 0, n
+        if self.prioritized:
+            if d.get("priorities") is not None:
+                self._q[:n].copy_(torch.as_tensor(d["priorities"], dtype=torch.float32)[:n].to(dev))
+            else:
+                self._init_priorities(0, n)
