@@ -126,6 +126,11 @@ SIGNATURES = {
     "mzba_adam_dev": [P, P, P, P, LL, P, P],
     "mzba_learner_input": [I, P, P, P, P, P, I, I, I, I, P],
     "mzba_dyn_input": [I, P, P, P, I, I, P, I, I, I, I, I, P],
+    # weight hand-off on the device (pack_fold.hip)
+    "mzba_pack_fold_job_bytes": [],
+    "mzba_pack_fold_bn_bytes": [],
+    "mzba_pack_fold_bn": [P, P, I, I, P],
+    "mzba_pack_fold": [P, P, I, I, P],
 }
 
 _lib = None

@@ -240,6 +240,22 @@ class PackedNets:
         for a, b in zip(mine, theirs):
             a.copy_(b)
 
+    def refresh_from_learner(self, learner):
+        """Write a `Learner`'s current master weights and running statistics into this pack's device buffers in place,
+        on the current stream (mzba/refresh.py + csrc/pack_fold.hip): the bits `PackedNets(learner.state_dict(), ...)`
+        would hold, without the host round trip — a fixed pair of launches, no host synchronisation once the job table
+        exists (it is built at the first call for a learner, and again after that learner's load_state_dict), so a
+        later call can be captured in a graph (to be captured again after that learner's load_state_dict: its
+        running-stat tensors are new). Ordering against acting is the caller's, through the stream, as for
+        refresh_from. bf16 packs, with or without the fp16 dynamics copies; ValueError (nothing written) for a learner
+        of another configuration, NotImplementedError naming a pack tensor the job table does not cover."""
+        from .refresh import RefreshTable
+        tab = getattr(self, "_refresh_table", None)
+        if tab is None or tab[0] is not learner or tab[1].stale(learner):
+            tab = (learner, RefreshTable(learner, self))
+            self._refresh_table = tab
+        tab[1].run()
+
     def _fused(self, sd, w0):
         """Weights of the fused dynamics / prediction steps (mzba_tower_fused): the dynamics
         ConvBlock and the head convs in the tower packings, next to the existing linear heads."""
@@ -693,6 +709,8 @@ class MuZeroAgent:
         self._learner = None      # train mode: the device learner (created by the first train_mode())
         self._training = False
         self._host_stale = False  # the learner's weights moved since the host copy was taken
+        self._snap = None         # refresh_from_learner: device clones of the source learner's state at the call
+        self._snap_stale = False  # the host copy has not been rebuilt from them yet
         self._optimizer = LearnerOptimizer(self)
         self._set_host(torch_init_state_dict(cfg))
 
@@ -711,8 +729,11 @@ class MuZeroAgent:
             else:
                 out[k] = torch.nn.Parameter(t.to(torch.float32))
         self._sd = out
+        self._snap_stale = False
 
     def _sync_host(self):
+        if self._snap_stale:  # the last refresh_from_learner: the host copy from its device snapshot, on demand
+            self._set_host(self._snapshot_state_dict())
         if self._learner is not None and self._host_stale:
             self._set_host(self._learner.state_dict())
             self._host_stale = False
@@ -731,6 +752,7 @@ class MuZeroAgent:
         return (v for _, v in self.named_parameters())
 
     def buffers(self):
+        self._sync_host()
         return (v for k, v in self._sd.items() if not isinstance(v, torch.nn.Parameter))
 
     def load_state_dict(self, sd):
@@ -748,6 +770,48 @@ class MuZeroAgent:
             self._learner.begin_calls()
         if self._packed is not None:  # a refresh: new weights into the existing buffers, live loops and
             self._packed.refresh_from(self._pack())  # captured graphs run them from their next launch
+
+    def refresh_from_learner(self, learner):
+        """The target-net refresh from a `Learner` this agent does not own (the fused bf16 learner of the throughput
+        path): its current weights and running statistics into the packed inference nets in place, on the device and on
+        the current stream (PackedNets.refresh_from_learner: no host synchronisation, live runners and captured
+        acting graphs run the new weights from their next launch on). `state_dict()` / `parameters()` afterwards are
+        `learner.state_dict()` as of this call: the learner's flat buffer and running statistics are cloned on the
+        device in the same stream, and the host copy is rebuilt from the clone when someone asks for it. An f32 agent,
+        and one that trains through its own learner, take the host path (load_state_dict(learner.state_dict()))."""
+        if self.dtype != "bf16" or self._learner is not None:
+            self.load_state_dict(learner.state_dict())
+            return
+        from .refresh import check_config
+        check_config(learner.m, self.cfg)
+        self.packed.refresh_from_learner(learner)
+        snap = self._snap
+        if snap is None or snap["learner"] is not learner or snap["run_ref"] is not learner.run:
+            snap = {"learner": learner, "run_ref": learner.run, "P": torch.empty_like(learner.P),
+                    "run": {k: (torch.empty_like(m), torch.empty_like(v)) for k, (m, v) in learner.run.items()}}
+            self._snap = snap
+        snap["P"].copy_(learner.P)
+        torch._foreach_copy_([t for k in learner.run for t in snap["run"][k]],  # one launch, not two per BatchNorm
+                             [t for k in learner.run for t in learner.run[k]])
+        snap["nbt"] = dict(learner.nbt)
+        self._snap_stale = True
+
+    def _snapshot_state_dict(self):
+        """learner.state_dict() as of the last refresh_from_learner, from the device snapshot."""
+        snap = self._snap
+        ln = snap["learner"]
+        out = OrderedDict()
+        for key, _ in state_dict_spec(self.cfg):
+            if key in ln.params:
+                p = ln.params[key]
+                out[key] = p.to_ref(snap["P"][p.off:p.off + p.n].view(p.kshape))
+            else:
+                bn, leaf = key.rsplit(".", 1)
+                if leaf == "num_batches_tracked":
+                    out[key] = torch.tensor(snap["nbt"][bn], dtype=torch.int64)
+                else:
+                    out[key] = snap["run"][bn][leaf == "running_var"].detach().cpu().clone()
+        return out
 
     def _pack(self):
         return PackedNets({k: _np(v) for k, v in self._sd.items()}, self.cfg, self.dtype, self.device, self.dyn_dtype)
@@ -774,6 +838,7 @@ class MuZeroAgent:
         three nets then run on the device learner's kernels and back-propagate through torch.autograd."""
         if self._learner is None:
             from .learner import Learner
+            self._sync_host()
             self._learner = Learner(self.cfg, {k: _np(v) for k, v in self._sd.items()}, dtype="f32",
                                     device=self.device, streams=1, defer_wgrad=False, fuse_bn=False)
             self._anchor = torch.zeros(1, device=self.device, requires_grad=True)
