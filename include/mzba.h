@@ -558,7 +558,7 @@ int mzba_conv_pack_bf16(const float* w, void* out, int Cout, int taps, int Cin, 
  * w[j], out[j] (16-B aligned), prm[8 j .. 8 j + 7] = {Cout, taps, Cin, N, Cc, flip, layout, pad} (pad % 8 == 0);
  * host arrays; the same outputs as the separate calls. */
 int mzba_conv_pack_bf16_multi(const float* const* w, void* const* out, const int* prm, int njobs, hipStream_t stream);
-/* Weight hand-off on the device (csrc/pack_fold.hip): the acting nets' packs from the learner's
+/* Weight hand-off on the device (csrc/pack.hip): the acting nets' packs from the learner's
  * f32 master weights and BN running statistics, bit-equal to the host packer (f64 fold, then f32, then bf16 / fp16).
  * Both tables live in device memory and are written by mzba/refresh.py (record sizes: the two _bytes entries);
  * first[i] = the first 256-thread workgroup of record i, nblocks = their total. mzba_pack_fold_bn writes every

@@ -9,14 +9,19 @@
 #define MZ_DEV __device__ __forceinline__
 
 // hipFuncAttributeMaxDynamicSharedMemorySize for a kernel, set once per kernel pointer (a launch helper
-// shared by several template instances must not key the one-time flag on the helper: ADVICE r4)
+// shared by several template instances must not key the one-time flag on the helper: ADVICE r4). Returns the
+// attribute call's error (hipSuccess when it was already set); a failed call is not remembered, so the next
+// launch tries again.
 #include <mutex>
 #include <set>
-inline void mz_set_lds_max_once(const void* kern, int bytes) {
+inline hipError_t mz_set_lds_max_once(const void* kern, int bytes) {
   static std::mutex mu;
   static std::set<const void*> done;
   std::lock_guard<std::mutex> lk(mu);
-  if (done.insert(kern).second) (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (done.count(kern)) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) done.insert(kern);
+  return e;
 }
 
 // ------------------------------------------------------------------ error plumbing
@@ -52,6 +57,29 @@ template <> struct ElemIO<bf16_t> {
   static MZ_DEV float load(const bf16_t* p) { return bf16_to_f32(*p); }
   static MZ_DEV void store(bf16_t* p, float v) { *p = f32_to_bf16(v); }
 };
+template <typename T> MZ_DEV float ld(const T* p) { return ElemIO<T>::load(p); }
+template <typename T> MZ_DEV void st(T* p, float v) { ElemIO<T>::store(p, v); }
+
+// ------------------------------------------------------------------ launch helpers (learn.hip, pack.hip, wgrad.hip)
+// grid of a grid-stride kernel over n elements
+static inline unsigned grid_for(size_t n, int block = 256, unsigned cap = 16384) {
+  size_t g = (n + block - 1) / block;
+  if (g < 1) g = 1;
+  return (unsigned)(g > cap ? cap : g);
+}
+
+// f(float{}) or f(bf16_t{}) by the C ABI's dtype code (0 = f32, 1 = bf16); -9 for any other
+template <typename F>
+int dispatch(int dtype, F&& f) {
+  if (dtype == 0) return f(float{});
+  if (dtype == 1) return f(bf16_t{});
+  return -9;
+}
+
+// acc[i] += the sum of a split launch's nsplit partials, bacc[j] likewise (sum_partials2_kernel, wgrad.hip), one launch
+// on `stream`: the heads' Linear backward (learn.hip) reduces its partials with the weight gradient's kernel
+__attribute__((visibility("hidden"))) void mz_sum_partials2(const float* part, const float* bpart, int nsplit, size_t n,
+                                                            size_t nb, float* acc, float* bacc, hipStream_t stream);
 
 // ------------------------------------------------------------------ Philox4x32-10
 // Bit-identical to oracle/rng.py. Counter = (global env, stream, step, call).

@@ -509,13 +509,8 @@ int launch_conv(const ConvArgs& a, hipStream_t s) {
   const bool span32 = ((long long)a.B * a.in_env_stride) / 8 < 0x7fff0000LL;
   if (sizeof(T) == 2 && g_conv_big && a.Cout % 256 == 0 && a.Cin % 64 == 0 && !a.act_bias && !a.slot &&
       M >= 64 * 1024 && span32) {
-    static bool attr = false;
-    if (!attr) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_big_bf16_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 4 * big::TILE);
-      if (e != hipSuccess) return (int)e;
-      attr = true;
-    }
+    const hipError_t e = mz_set_lds_max_once(reinterpret_cast<const void*>(&conv_big_bf16_kernel), 4 * big::TILE);
+    if (e != hipSuccess) return (int)e;
     dim3 grid((M + big::BM - 1) / big::BM, a.Cout / big::BN);
     hipLaunchKernelGGL(conv_big_bf16_kernel, grid, dim3(big::NT), 4 * big::TILE, s, a);
     MZ_LAUNCH_CHECK();

@@ -983,7 +983,7 @@ void x6t_launch(const X6TArgs& t, int ks, bool ga, hipStream_t stream, int force
   const int nw = force_nw ? force_nw : g_x6t_waves ? g_x6t_waves : (t16 * (t.Cout / 128) < x6p_ncu() ? 4 : 8);
   const dim3 grid((unsigned)t16, (unsigned)(t.Cout / (16 * nw)));
   auto launch = [&](auto kern, int nthreads) {
-    mz_set_lds_max_once(reinterpret_cast<const void*>(kern), x6::LDS_MAX);
+    (void)mz_set_lds_max_once(reinterpret_cast<const void*>(kern), x6::LDS_MAX);
     hipLaunchKernelGGL(kern, grid, dim3(nthreads), x6t::lds(NP, PIPE), stream, t);
   };
   if (nw == 4) {
@@ -1117,7 +1117,7 @@ int x6_halo_launch(const void* in, const void* wx, const float* bias, const void
     const int ldsp = ap.ZOFF + 3 * (Cin / geo.nblk) * 2;
     const dim3 gridp((unsigned)((M + tmp - 1) / tmp), (unsigned)(Cout / (128 * geo.ct)));
     auto launchp = [&](auto kern) {
-      mz_set_lds_max_once(reinterpret_cast<const void*>(kern), x6::LDS_MAX);
+      (void)mz_set_lds_max_once(reinterpret_cast<const void*>(kern), x6::LDS_MAX);
       hipLaunchKernelGGL(kern, gridp, dim3(x6::NT), ldsp, stream, ap);
     };
     if (tmp == 160) {  // the 16x20 instances
@@ -1155,7 +1155,7 @@ int x6_halo_launch(const void* in, const void* wx, const float* bias, const void
   const int lds = a.ZOFF + 16 * Cin * 4;
   const dim3 grid((unsigned)((M + tm - 1) / tm), (unsigned)(Cout / x6::TN));
   auto launch = [&](auto kern) {
-    mz_set_lds_max_once(reinterpret_cast<const void*>(kern), x6::LDS_MAX);
+    (void)mz_set_lds_max_once(reinterpret_cast<const void*>(kern), x6::LDS_MAX);
     hipLaunchKernelGGL(kern, grid, dim3(x6::NT), lds, stream, a);
   };
   if (Cin == 256)
@@ -1194,7 +1194,7 @@ int x3_halo_launch(const void* in, const void* wx3, const float* wscale, const f
   const int ldsp = ap.ZOFF + 2 * (Cin / geo.nblk) * 2;
   const dim3 gridp((unsigned)((M + tm - 1) / tm), (unsigned)(Cout / (128 * geo.ct)));
   auto launchp = [&](auto kern) {
-    mz_set_lds_max_once(reinterpret_cast<const void*>(kern), x6::LDS_MAX);
+    (void)mz_set_lds_max_once(reinterpret_cast<const void*>(kern), x6::LDS_MAX);
     hipLaunchKernelGGL(kern, gridp, dim3(x6::NT), ldsp, stream, ap);
   };
   if (tm == 160) {

@@ -89,7 +89,7 @@ SIGNATURES = {
     "mzba_torch_pow": [P, P, LL, D, LL, LL, I, I, P],
     "mzba_record_results": [P, P, P, P, I, I, P, P],
     "mzba_ctx_advance": [P, P],
-    # learner (learn.hip)
+    # learner (learn.hip; mzba_conv_wpack / mzba_conv_pack_bf16* in pack.hip, mzba_conv_wgrad* in wgrad.hip)
     "mzba_bn_stats": [I, P, I, I, F, F, P, P, P, P, P, P, LL, P],
     "mzba_bn_apply": [I, P, P, P, I, P, I, I, P],
     "mzba_bn_backward": [I, P, P, P, P, I, I, P, P, P, P, LL, P],
@@ -126,7 +126,7 @@ SIGNATURES = {
     "mzba_adam_dev": [P, P, P, P, LL, P, P],
     "mzba_learner_input": [I, P, P, P, P, P, I, I, I, I, P],
     "mzba_dyn_input": [I, P, P, P, I, I, P, I, I, I, I, I, P],
-    # weight hand-off on the device (pack_fold.hip)
+    # weight hand-off on the device (pack.hip)
     "mzba_pack_fold_job_bytes": [],
     "mzba_pack_fold_bn_bytes": [],
     "mzba_pack_fold_bn": [P, P, I, I, P],

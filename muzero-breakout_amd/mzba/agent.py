@@ -15,12 +15,10 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .weights import rep_layout, state_dict_spec, torch_init_state_dict
+from .weights import BN_EPS, LAT_PAD_ELEMS, _round64, rep_layout, state_dict_spec, torch_init_state_dict
 
-BN_EPS = 1e-5
 DT_CODE = {"f32": 0, "bf16": 1}
 TORCH_DT = {"f32": torch.float32, "bf16": torch.bfloat16}
-LAT_PAD_ELEMS = 8 * 64 * 8  # conv_lat weight-ring overrun: 8 k steps x 64 lanes x 8 bf16
 
 
 def _np(x):
@@ -81,10 +79,6 @@ def pack_tower_conv(w):
     return pack_lat16(np.ascontiguousarray(w.transpose(0, 3, 2, 1)).reshape(cout, -1), cout, 3, cin)
 
 
-def _round64(c):
-    return (c + 63) // 64 * 64
-
-
 class PackedNets:
     """Device-resident packed weights for one precision."""
 
@@ -111,7 +105,8 @@ class PackedNets:
             p = f"rep_net.blocks.{i}"
             if kind == "conv":
                 cout = self.c0 if nconv == 0 else self.c1
-                self.rep.append(("conv", self._conv(sd[p + ".weight"], sd[p + ".bias"], None, band=True, hw=hw)))
+                self.rep.append(("conv", self._conv(*self._folded(sd, p + ".weight", p + ".bias", None), band=True,
+                                                    hw=hw)))
                 nconv += 1
                 cin = cout
             elif kind == "res":
@@ -120,15 +115,12 @@ class PackedNets:
                 self.rep.append(("pool", None))
                 hw = (hw[0] // 2, hw[1] // 2)
         # dynamics (networks.py:117-149)
-        w = sd["dyn_net.conv_block.conv.weight"]
-        cmain = self.c1
         lat = (self.lh, self.lw)
-        self.dyn0 = self._conv(w[:, :cmain], sd["dyn_net.conv_block.conv.bias"], self._bn(sd, "dyn_net.conv_block.bn"),
-                               act_w=w[:, cmain:], hw=lat)
+        w, b = self._block(sd, "dyn_net.conv_block")  # the action planes are its input channels from c1 on
+        self.dyn0 = self._conv(w[:, :self.c1], b, act_w=w[:, self.c1:], hw=lat)
         self.dyn = [self._res(sd, f"dyn_net.res_blocks.{i}", hw=lat)
                     for i in range(mcfg["dynamics_network"]["num_res_blocks"])]
-        self.rew_conv = self._conv(sd["dyn_net.reward_head.0.conv.weight"], sd["dyn_net.reward_head.0.conv.bias"],
-                                   self._bn(sd, "dyn_net.reward_head.0.bn"), hw=lat)
+        self.rew_conv = self._conv(*self._block(sd, "dyn_net.reward_head.0"), hw=lat)
         self.rew_lin = self._linear(sd["dyn_net.reward_head.2.weight"], sd["dyn_net.reward_head.2.bias"], self.c1)
         # prediction (networks.py:190-223)
         self.pred = [self._res(sd, f"pred_net.res_blocks.{i}", hw=lat)
@@ -138,13 +130,11 @@ class PackedNets:
         self.tower_ok = (self.dtype == "bf16" and self.c1 == 256 and (self.lh, self.lw) == (4, 5))
         self.dyn_tower = self._tower(sd, "dyn_net.res_blocks", mcfg["dynamics_network"]["num_res_blocks"])
         self.pred_tower = self._tower(sd, "pred_net.res_blocks", mcfg["prediction_network"]["num_res_blocks"])
-        self.pol_conv = self._conv(sd["pred_net.policy_head.0.conv.weight"], sd["pred_net.policy_head.0.conv.bias"],
-                                   self._bn(sd, "pred_net.policy_head.0.bn"), hw=lat)
+        self.pol_conv = self._conv(*self._block(sd, "pred_net.policy_head.0"), hw=lat)
         self.pol_lin = self._linear(sd["pred_net.policy_head.2.weight"], sd["pred_net.policy_head.2.bias"], self.c1 // 2)
-        self.val_conv = self._conv(sd["pred_net.value_head.0.conv.weight"], sd["pred_net.value_head.0.conv.bias"],
-                                   self._bn(sd, "pred_net.value_head.0.bn"), hw=lat)
+        self.val_conv = self._conv(*self._block(sd, "pred_net.value_head.0"), hw=lat)
         self.val_lin = self._linear(sd["pred_net.value_head.2.weight"], sd["pred_net.value_head.2.bias"], self.c1 // 2)
-        self.fused = self._fused(sd, w[:, :cmain])
+        self.fused = self._fused(sd)
         self.rep_tail = self._rep_tail(sd)
         self.rep_blocks = self._rep_blocks(sd)
         self.native = self._native()
@@ -242,7 +232,7 @@ class PackedNets:
 
     def refresh_from_learner(self, learner):
         """Write a `Learner`'s current master weights and running statistics into this pack's device buffers in place,
-        on the current stream (mzba/refresh.py + csrc/pack_fold.hip): the bits `PackedNets(learner.state_dict(), ...)`
+        on the current stream (mzba/refresh.py + csrc/pack.hip): the bits `PackedNets(learner.state_dict(), ...)`
         would hold, without the host round trip — a fixed pair of launches, no host synchronisation once the job table
         exists (it is built at the first call for a learner, and again after that learner's load_state_dict), so a
         later call can be captured in a graph (to be captured again after that learner's load_state_dict: its
@@ -256,16 +246,12 @@ class PackedNets:
             self._refresh_table = tab
         tab[1].run()
 
-    def _fused(self, sd, w0):
+    def _fused(self, sd):
         """Weights of the fused dynamics / prediction steps (mzba_tower_fused): the dynamics
         ConvBlock and the head convs in the tower packings, next to the existing linear heads."""
         if not (self.dyn_tower and self.pred_tower and "wb" in self.rew_lin and "wb" in self.pol_lin
                 and "wb" in self.val_lin and self.c1 // 2 == 128 and self.ns <= 16):
             return None
-
-        def fold(cw, cb, bn):
-            alpha, beta = self._bn(sd, bn)
-            return cw * alpha[:, None, None, None], cb * alpha + beta
 
         def dev(x, dt=None):
             return torch.tensor(np.asarray(x), dtype=torch.float32).to(dt or torch.float32).to(self.device)
@@ -278,14 +264,11 @@ class PackedNets:
             return dev(np.concatenate([pack_lat16(cw.reshape(co, ci), co, 1, ci), np.zeros(LAT_PAD_ELEMS)]),
                        dt or self.tdt)
 
-        a0, b0 = self._bn(sd, "dyn_net.conv_block.bn")
-        rw, rb = fold(sd["dyn_net.reward_head.0.conv.weight"], sd["dyn_net.reward_head.0.conv.bias"],
-                      "dyn_net.reward_head.0.bn")
-        pw, pb = fold(sd["pred_net.policy_head.0.conv.weight"], sd["pred_net.policy_head.0.conv.bias"],
-                      "pred_net.policy_head.0.bn")
-        vw, vb = fold(sd["pred_net.value_head.0.conv.weight"], sd["pred_net.value_head.0.conv.bias"],
-                      "pred_net.value_head.0.bn")
-        out = {"w0": pack3(w0 * a0[:, None, None, None]), "b0": self.dyn0["b"], "act_bias": self.dyn0["act_bias"],
+        w0 = self._block(sd, "dyn_net.conv_block")[0][:, :self.c1]  # without the action planes
+        rw, rb = self._block(sd, "dyn_net.reward_head.0")
+        pw, pb = self._block(sd, "pred_net.policy_head.0")
+        vw, vb = self._block(sd, "pred_net.value_head.0")
+        out = {"w0": pack3(w0), "b0": self.dyn0["b"], "act_bias": self.dyn0["act_bias"],
                "A": self.dyn0["A"], "rw": pack1(rw), "rb": dev(rb), "pw": pack3(pw), "pb": dev(pb),
                "vw": pack1(vw), "vb": dev(vb)}
         if self.dyn_fp16:  # the dynamics step's fp16 weights (its tower pack: dyn_tower['wf16'])
@@ -294,7 +277,7 @@ class PackedNets:
             lw = np.zeros((16, K))
             lw[:O] = w.reshape(O, self.c1, K // self.c1).transpose(0, 2, 1).reshape(O, K)
             lw = dev(lw, torch.float16)
-            out["dyn16"] = {"w0": pack3(w0 * a0[:, None, None, None], torch.float16), "rw": pack1(rw, torch.float16),
+            out["dyn16"] = {"w0": pack3(w0, torch.float16), "rw": pack1(rw, torch.float16),
                             "lw": lw}
         return out
 
@@ -313,17 +296,8 @@ class PackedNets:
             i -= 1
         if i < 0 or lay[i][0] != "pool" or not 1 <= len(blocks) <= 24:
             return None
-        ws, bs = [], []
-        for j in blocks:
-            for k in (1, 2):
-                p = f"rep_net.blocks.{j}"
-                alpha, beta = self._bn(sd, f"{p}.bn{k}")
-                ws.append(sd[f"{p}.conv{k}.weight"] * alpha[:, None, None, None])
-                bs.append(sd[f"{p}.conv{k}.bias"] * alpha + beta)
-        wf = np.concatenate([pack_tower_conv(w) for w in ws] + [np.zeros(LAT_PAD_ELEMS)])
-        return {"n": len(blocks), "first": len(lay) - 2 - len(blocks),  # rep_layout index of the first pool
-                "wf": torch.tensor(wf, dtype=torch.float32).to(self.tdt).to(self.device),
-                "b": torch.tensor(np.concatenate(bs), dtype=torch.float32, device=self.device)}
+        # first: the rep_layout index of the first pool
+        return {**self._tower_pack(sd, [f"rep_net.blocks.{j}" for j in blocks]), "first": len(lay) - 2 - len(blocks)}
 
     def _rep_blocks(self, sd):
         """Weights of mzba_rep_blocks: the run of 256-channel residual blocks at full resolution that
@@ -342,19 +316,9 @@ class PackedNets:
         # 256-channel blocks only: the run starts after the conv that widens to c1
         if not blocks or i < 0 or lay[i][0] != "conv" or len(blocks) > 24:
             return None
-        ws, bs = [], []
-        for j in blocks:
-            for k in (1, 2):
-                p = f"rep_net.blocks.{j}"
-                alpha, beta = self._bn(sd, f"{p}.bn{k}")
-                ws.append(sd[f"{p}.conv{k}.weight"] * alpha[:, None, None, None])
-                bs.append(sd[f"{p}.conv{k}.bias"] * alpha + beta)
-        if any(w.shape[:2] != (256, 256) for w in ws):
+        if any(sd[f"rep_net.blocks.{j}.conv{k}.weight"].shape[:2] != (256, 256) for j in blocks for k in (1, 2)):
             return None
-        wf = np.concatenate([pack_tower_conv(w) for w in ws] + [np.zeros(LAT_PAD_ELEMS)])
-        return {"n": len(blocks), "first": i + 1,
-                "wf": torch.tensor(wf, dtype=torch.float32).to(self.tdt).to(self.device),
-                "b": torch.tensor(np.concatenate(bs), dtype=torch.float32, device=self.device)}
+        return {**self._tower_pack(sd, [f"rep_net.blocks.{j}" for j in blocks]), "first": i + 1}
 
     # -- packing helpers ---------------------------------------------------------------
     @staticmethod
@@ -363,13 +327,36 @@ class PackedNets:
         alpha = g / np.sqrt(v + BN_EPS)
         return alpha, b - m * alpha
 
-    def _conv(self, w, bias, bn, act_w=None, band=False, hw=None):
-        """hw: the (H, W) the conv runs at, when known: large images get the halo-tiled kernel's packing."""
+    @classmethod
+    def _folded(cls, sd, kw, kb, bn):
+        """The conv sd[kw] (OIHW) / sd[kb] with the BatchNorm of prefix `bn` folded in (None: no BatchNorm): (w, b),
+        f64. The one statement of the fold on the host; csrc/pack.hip's pack_fold kernels are the device's."""
+        w, b = sd[kw], sd[kb]
+        if bn is None:
+            return w, b
+        alpha, beta = cls._bn(sd, bn)
+        return w * alpha[:, None, None, None], b * alpha + beta
+
+    @classmethod
+    def _block(cls, sd, p):
+        """_folded of a ConvBlock (conv + BatchNorm) of prefix p."""
+        return cls._folded(sd, p + ".conv.weight", p + ".conv.bias", p + ".bn")
+
+    def _tower_pack(self, sd, prefixes, fp16=False):
+        """Every conv of the residual blocks `prefixes`, folded, back to back in pack_tower_conv order + the ring's
+        pad ("wf"; fp16: and its fp16 copy "wf16"), their biases back to back ("b"), and the block count ("n")."""
+        ws, bs = zip(*(self._folded(sd, f"{p}.conv{k}.weight", f"{p}.conv{k}.bias", f"{p}.bn{k}")
+                       for p in prefixes for k in (1, 2)))
+        wf = torch.tensor(np.concatenate([pack_tower_conv(w) for w in ws] + [np.zeros(LAT_PAD_ELEMS)]),
+                          dtype=torch.float32)
+        return {"n": len(prefixes), "wf": wf.to(self.tdt).to(self.device),
+                "b": torch.tensor(np.concatenate(bs), dtype=torch.float32, device=self.device),
+                **({"wf16": wf.to(torch.float16).to(self.device)} if fp16 else {})}
+
+    def _conv(self, w, bias, act_w=None, band=False, hw=None):
+        """One conv layer's packs from its folded (w, bias); act_w: the folded weights of the action planes.
+        hw: the (H, W) the conv runs at, when known: large images get the halo-tiled kernel's packing."""
         cout, cin, k, _ = w.shape
-        if bn is not None:
-            alpha, beta = bn
-            w = w * alpha[:, None, None, None]
-            bias = bias * alpha + beta
         cin_p = _round64(cin)
         wp = np.zeros((cout, k, k, cin_p), dtype=np.float64)
         wp[..., :cin] = w.transpose(0, 2, 3, 1)
@@ -378,9 +365,7 @@ class PackedNets:
             "b": torch.tensor(bias, dtype=torch.float32, device=self.device),
             "cin": cin_p, "cout": cout, "ks": k, "act_bias": None,
         }
-        if act_w is not None:  # (cout, A, k, k) scaled by alpha: per-(pixel, action) bias
-            if bn is not None:
-                act_w = act_w * bn[0][:, None, None, None]
+        if act_w is not None:  # (cout, A, k, k): per-(pixel, action) bias
             A = act_w.shape[1]
             H, W = self.lh, self.lw
             tab = np.zeros((H * W, A, cout))
@@ -420,27 +405,16 @@ class PackedNets:
         return layer
 
     def _res(self, sd, p, band=False, hw=None):
-        return (self._conv(sd[p + ".conv1.weight"], sd[p + ".conv1.bias"], self._bn(sd, p + ".bn1"), band=band, hw=hw),
-                self._conv(sd[p + ".conv2.weight"], sd[p + ".conv2.bias"], self._bn(sd, p + ".bn2"), band=band, hw=hw))
+        return tuple(self._conv(*self._folded(sd, f"{p}.conv{k}.weight", f"{p}.conv{k}.bias", f"{p}.bn{k}"), band=band,
+                                hw=hw) for k in (1, 2))
 
     def _tower(self, sd, prefix, n):
         if not self.tower_ok or n == 0:
             return None
-        ws, bs = [], []
-        for i in range(n):
-            for k in (1, 2):
-                p = f"{prefix}.{i}"
-                alpha, beta = self._bn(sd, f"{p}.bn{k}")
-                ws.append(sd[f"{p}.conv{k}.weight"] * alpha[:, None, None, None])
-                bs.append(sd[f"{p}.conv{k}.bias"] * alpha + beta)
         # every tower kernel (plans 1-3) takes the same packing: all convs back to back, + the ring's
         # 8 padding k steps; the fp16 dynamics net (config 5) has its own copy
-        wf = np.concatenate([pack_tower_conv(w) for w in ws] + [np.zeros(LAT_PAD_ELEMS)])
-        tw = {"n": n, "b": torch.tensor(np.concatenate(bs), dtype=torch.float32, device=self.device),
-              "wf": torch.tensor(wf, dtype=torch.float32).to(self.tdt).to(self.device)}
-        if self.dyn_fp16 and prefix.startswith("dyn"):
-            tw["wf16"] = torch.tensor(wf, dtype=torch.float32).to(torch.float16).to(self.device)
-        return tw
+        return self._tower_pack(sd, [f"{prefix}.{i}" for i in range(n)],
+                                fp16=self.dyn_fp16 and prefix.startswith("dyn"))
 
     def _linear(self, w, b, c):
         O, K = w.shape

@@ -1,7 +1,7 @@
 """Device learner: the training side of the reference's RLSystem.
 
 One minibatch of `RLSystem._training_stage` (train_torch.py:380-407) runs as a sequence of
-HIP launches over NHWC device buffers (csrc/learn.hip + the implicit-GEMM conv of conv.hip):
+HIP launches over NHWC device buffers (csrc/learn.hip, pack.hip, wgrad.hip + the implicit-GEMM conv of conv.hip):
 
   _prepare_minibatch + _encode_actions   mzba_learner_input (frames + a/3 planes straight from the
                                           replay ring, no host gather)
@@ -30,17 +30,11 @@ import torch
 
 from . import _lib as L
 from .env import gray_lut
-from .weights import init_state_dict, rep_layout, state_dict_spec
+from .weights import BN_EPS, LAT_PAD_ELEMS, _pad8, init_state_dict, rep_layout, state_dict_spec
 
-LAT_PAD_ELEMS = 8 * 64 * 8  # conv_lat / band weight-ring overrun (agent.LAT_PAD_ELEMS)
-
-BN_EPS, BN_MOMENTUM = 1e-5, 0.1
+BN_MOMENTUM = 0.1
 CTR_WORDS = 8192  # BN finaliser counter words per minibatch (about 2 x 632 used at the reference architecture)
 BETAS, ADAM_EPS, WEIGHT_DECAY = (0.9, 0.999), 1e-8, 1e-4
-
-
-def _pad8(c):
-    return (c + 7) // 8 * 8
 
 
 class _Param:

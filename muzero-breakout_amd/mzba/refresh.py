@@ -1,7 +1,7 @@
 """Weight hand-off on the device: the acting nets' packs written from a `Learner`'s master weights.
 
 `PackedNets(sd, ...)` (agent.py) folds every BatchNorm and permutes every conv into its kernel packings on the host, in
-f64 numpy. This module states the same packing as a job table for csrc/pack_fold.hip: one job writes one destination
+f64 numpy. This module states the same packing as a job table for csrc/pack.hip: one job writes one destination
 tensor, or one slice of a concatenated one, from the learner's flat f32 buffer (`Learner.P`, already
 [Cout][tap][Cin_pad8] / [O][pixel][C]) and its running statistics, with the host packer's bits.
 
@@ -17,11 +17,9 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .weights import rep_layout
+from .weights import LAT_PAD_ELEMS, _pad8, _round64, rep_layout  # LAT_PAD_ELEMS: trailing zeros never written here
 
-LAT_PAD_ELEMS = 8 * 64 * 8  # agent.LAT_PAD_ELEMS: the weight rings' trailing zeros (never written here)
-
-PLAIN, LAT, LAT16, BIAS, ACT = range(5)  # csrc/pack_fold.hip PF_*
+PLAIN, LAT, LAT16, BIAS, ACT = range(5)  # csrc/pack.hip PF_*
 OTYPE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 JOB_DT = np.dtype([("w", "<u8"), ("ab", "<u8"), ("dst", "<u8"), ("off", "<i8"), ("kind", "<i4"), ("otype", "<i4"),
@@ -37,14 +35,6 @@ CFG_KEYS = (("latent_channels",), ("latent_resolution",), ("state_history_length
             ("representation_network", "num_res_blocks"), ("dynamics_network", "num_res_blocks"),
             ("dynamics_network", "num_actions"), ("prediction_network", "num_res_blocks"),
             ("prediction_network", "num_actions"))
-
-
-def _pad8(c):
-    return (c + 7) // 8 * 8
-
-
-def _round64(c):
-    return (c + 63) // 64 * 64
 
 
 def named_tensors(pack):

@@ -262,9 +262,9 @@ def test_learner_optimizer_param_groups_persist_and_lr_writes_reach_the_learner(
 
 
 def test_learner_entry_points_reject_bad_arguments_without_gpu():
-    """Every learner entry point of csrc/learn.hip that tests/test_gpu_learner_ops.py covers checks its arguments
-    before any HIP call: otherwise valid (dummy, non-null) arguments with one violation each return the documented
-    code. Runs only where no GPU is visible, so a missing check can never launch a kernel on the dummy pointers."""
+    """Every learner entry point of csrc/learn.hip and csrc/pack.hip that tests/test_gpu_learner_ops.py covers checks
+    its arguments before any HIP call: otherwise valid (dummy, non-null) arguments with one violation each return the
+    documented code. Runs only where no GPU is visible, so a missing check can never launch a kernel on the dummy pointers."""
     import ctypes
     import torch
     if torch.cuda.is_available():

@@ -1,7 +1,7 @@
 """The learner's small kernels (csrc/learn.hip: BatchNorm statistics / apply / backward, avg-pool backward, axpy,
-min-max scale, the Linear heads, the loss, Adam, the input builders, the batched weight pack), each called through
-the C ABI and compared with a float64 evaluation of the same operation on the CPU (plain torch / numpy) from the
-same, already rounded, inputs. No mzba_* entry point serves as a reference for another.
+min-max scale, the Linear heads, the loss, Adam, the input builders; csrc/pack.hip: the batched weight pack), each
+called through the C ABI and compared with a float64 evaluation of the same operation on the CPU (plain torch /
+numpy) from the same, already rounded, inputs. No mzba_* entry point serves as a reference for another.
 
 Error bounds (the idiom of test_conv_x6_is_as_close_to_exact_as_f32). e_k is the kernel's error against f64, e_w
 the error of a plain torch f32 CPU evaluation of the same operation (the witness, measured in the test) against

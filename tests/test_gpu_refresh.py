@@ -1,4 +1,4 @@
-"""Weight hand-off on the device (csrc/pack_fold.hip, mzba/refresh.py): PackedNets.refresh_from_learner /
+"""Weight hand-off on the device (csrc/pack.hip, mzba/refresh.py): PackedNets.refresh_from_learner /
 MuZeroAgent.refresh_from_learner against the host packer.
 
 The oracle is the host packer itself: for any learner state, PackedNets(learner.state_dict(), cfg, "bf16", device,
