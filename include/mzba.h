@@ -650,6 +650,67 @@ int mzba_learner_input(int dtype, const uint8_t* states, const int64_t* past_act
 int mzba_dyn_input(int dtype, const void* h, const int64_t* future_actions, const int32_t* slots, int K, int k,
                    void* out, int B, int HW, int C, int A, int Cp, hipStream_t stream);
 
+/* ---- Learner step guard (csrc/guard.hip): gradient norm, clipping, non-finite skip and the
+ * learning-rate schedule on the device, inside the captured minibatch. Opt-in (Learner(guard=...)).
+ *
+ * The stats block, one per learner, in device memory (8-byte aligned; mzba_guard_block_bytes() == sizeof).
+ * mzba_guard_finish rewrites every field each step; t_applied and skipped carry over from step to step and are
+ * seeded by the host (zero, or a checkpoint's step). */
+#define MZBA_GUARD_MAX_SEG 8
+typedef struct {
+  double norm;                              /*   0 sqrt of the sum of squares over all segments */
+  double seg_norm[MZBA_GUARD_MAX_SEG];      /*   8 per segment (0 beyond nseg) */
+  double seg_sumsq[MZBA_GUARD_MAX_SEG];     /*  72 per-segment sum of squares, f64 */
+  int32_t seg_nonfinite[MZBA_GUARD_MAX_SEG];/* 136 per-segment count of Inf / NaN elements */
+  float coef;                               /* 168 min(1, max_norm / (norm + 1e-6)); exactly 1 for max_norm = +inf */
+  int32_t nonfinite;                        /* 172 the counts' total */
+  int32_t loss_nonfinite;                   /* 176 how many of the four loss floats are Inf / NaN */
+  int32_t skip;                             /* 180 1: this step leaves weights, Adam state, statistics, priorities */
+  int32_t t_applied;                        /* 184 optimizer steps applied so far, this one included when skip == 0 */
+  int32_t skipped;                          /* 188 steps skipped so far */
+  float lr;                                 /* 192 the learning rate of step t_applied */
+  float sc[7];                              /* 196 Adam's scalars for t_applied, mzba_adam_dev's order */
+} mzba_guard_block;                         /* 224 bytes */
+int mzba_guard_block_bytes(void);
+/* One streaming pass over the flat f32 gradient g[n]. Segment s (nseg <= 8) is [seg_bounds[s], seg_bounds[s + 1]):
+ * nseg + 1 ascending host offsets inside [0, n], aligned to nothing; elements outside every segment are not read
+ * into any result. Per segment: the f64 sum of the squares, each square formed in double, and the count of
+ * non-finite elements. The pass writes partials into ws; mzba_guard_finish folds them.
+ * Reproducible and independent of the launch grid: chunk c = elements [16384 c, 16384 (c + 1)) belongs to partial
+ * c; inside a chunk element o belongs to thread (o / 4) % 256, which adds its squares in ascending o into four
+ * accumulators (o % 4), folded (a0 + a1) + (a2 + a3); lanes fold by the xor butterfly 32, 16, .. 1, waves in wave
+ * order; no floating-point atomics; workgroups stride over the chunks. 16-byte loads for a whole chunk inside one
+ * segment when g is 16-byte aligned, scalar loads otherwise, with the same lane assignment and therefore the same
+ * bits. loss4: the minibatch's four loss floats (device), whose non-finite count rides in ws; NULL: none.
+ * ws >= mzba_grad_stats_ws_bytes(n) bytes, 16-byte aligned. One launch, no host synchronisation.
+ * mzba_grad_stats_set_grid: tests only; workgroups of the next launches (0: the default). */
+long long mzba_grad_stats_ws_bytes(long long n);
+int mzba_grad_stats_set_grid(int blocks);
+int mzba_grad_stats(const float* g, long long n, const long long* seg_bounds, int nseg, const float* loss4, void* ws,
+                    long long ws_bytes, hipStream_t stream);
+/* One wave, after mzba_grad_stats on the same stream with the same n, nseg and ws. Lane l folds the partials of
+ * chunks [l per, (l + 1) per), per = ceil(chunks / 64), in index order; the lane totals are added in lane order.
+ * norm, coef as in the block's comments (a NaN norm under a finite max_norm gives a NaN coef, as
+ * torch.nn.utils.clip_grad_norm_). skip = skip_nonfinite && (nonfinite > 0 || loss_nonfinite > 0). skip == 0:
+ * t_applied += 1; else skipped += 1. With t = t_applied: lr = lr_dev ? lr_dev[0] : sched_steps > 0 ?
+ * lr0 rate^((t - 1) / sched_steps) : lr0, and sc = {-(lr / (1 - b1^t)), 1 - b1, b2, 1 - b2, sqrt(1 - b2^t), eps, wd},
+ * all in double, each rounded once to f32. max_norm > 0 (+inf: no clipping), sched_steps >= 0, sched_rate > 0. */
+int mzba_guard_finish(const void* ws, long long ws_bytes, long long n, int nseg, mzba_guard_block* block,
+                      double max_norm, int skip_nonfinite, double lr0, double sched_rate, int sched_steps,
+                      const float* lr_dev, double b1, double b2, double eps, double wd, hipStream_t stream);
+/* mzba_adam_dev's update with block->sc as the scalars and grad read as block->coef * grad (one f32 multiply,
+ * exact for coef == 1.0f: then mzba_adam_dev's bits). block->skip != 0: no load of the arrays and no store. */
+int mzba_adam_guard(float* p, const float* grad, float* m, float* v, long long n, const mzba_guard_block* block,
+                    hipStream_t stream);
+/* The BatchNorm running statistics around a guarded minibatch. table: ntensors records {float* live; float* snap;
+ * int32 n; int32 pad} (24 bytes) in device memory, one 256-thread workgroup each. snapshot: snap <- live, always;
+ * restore: live <- snap when block->skip != 0. */
+int mzba_guard_snapshot(const void* table, int ntensors, hipStream_t stream);
+int mzba_guard_restore(const void* table, int ntensors, const mzba_guard_block* block, hipStream_t stream);
+/* mzba_replay_priority_update that leaves q untouched when block->skip != 0 (csrc/replay_prio.hip). */
+int mzba_replay_priority_update_g(float* q, const int32_t* slots, const float* td, int n, int cap, float alpha,
+                                  float eps, const mzba_guard_block* block, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,18 @@ __global__ __launch_bounds__(256) void prio_update_kernel(float* __restrict__ q,
   q[slot] = prio_q(td[j], eps, alpha);
 }
 
+// prio_update_kernel under the learner's step guard (guard.hip): a skipped step leaves q as it is
+__global__ __launch_bounds__(256) void prio_update_g_kernel(float* __restrict__ q, const int32_t* __restrict__ slots,
+                                                            const float* __restrict__ td, int n, int cap, float alpha,
+                                                            float eps, const mzba_guard_block* __restrict__ blk) {
+  if (blk->skip) return;
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const int slot = slots[j];
+  if (slot < 0 || slot >= cap) return;
+  q[slot] = prio_q(td[j], eps, alpha);
+}
+
 // lane's 16 priorities of block b (0 past cap), 16-byte loads where the 16 are all inside
 MZ_DEV void load16(const float* __restrict__ q, int cap, int b, int lane, float* v) {
   const int i0 = b * PB + lane * 16;
@@ -216,6 +228,16 @@ int mzba_replay_priority_update(float* q, const int32_t* slots, const float* td,
   if (n == 0) return 0;
   hipLaunchKernelGGL(prio_update_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, q, slots, td, n, cap, alpha,
                      eps);
+  MZ_LAUNCH_CHECK();
+  return 0;
+}
+
+int mzba_replay_priority_update_g(float* q, const int32_t* slots, const float* td, int n, int cap, float alpha,
+                                  float eps, const mzba_guard_block* block, hipStream_t stream) {
+  MZ_CHECK_ARG(q && slots && td && block && n >= 0 && cap > 0 && alpha >= 0.f && eps >= 0.f, -1);
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(prio_update_g_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, q, slots, td, n, cap, alpha,
+                     eps, block);
   MZ_LAUNCH_CHECK();
   return 0;
 }

@@ -131,6 +131,16 @@ SIGNATURES = {
     "mzba_pack_fold_bn_bytes": [],
     "mzba_pack_fold_bn": [P, P, I, I, P],
     "mzba_pack_fold": [P, P, I, I, P],
+    # learner step guard (guard.hip; the guarded priority update in replay_prio.hip)
+    "mzba_guard_block_bytes": [],
+    "mzba_grad_stats_ws_bytes": [LL],
+    "mzba_grad_stats_set_grid": [I],
+    "mzba_grad_stats": [P, LL, P, I, P, P, LL, P],
+    "mzba_guard_finish": [P, LL, LL, I, P, D, I, D, D, I, P, D, D, D, D, P],
+    "mzba_adam_guard": [P, P, P, P, LL, P, P],
+    "mzba_guard_snapshot": [P, I, P],
+    "mzba_guard_restore": [P, I, P, P],
+    "mzba_replay_priority_update_g": [P, P, P, I, I, F, F, P, P],
 }
 
 _lib = None
@@ -156,7 +166,8 @@ class TowerExt(ctypes.Structure):
 
 # entry points that return something other than a status code
 RESTYPES = {"mzba_tower_ws_bytes": LL, "mzba_tower_plan": I, "mzba_conv_lat_get_variant": I, "mzba_conv_wgrad_ws_bytes": LL,
-            "mzba_linear_ws_bytes": LL, "mzba_learner_loss_ws_bytes": LL, "mzba_replay_sample_ws_bytes": LL}
+            "mzba_linear_ws_bytes": LL, "mzba_learner_loss_ws_bytes": LL, "mzba_replay_sample_ws_bytes": LL,
+            "mzba_grad_stats_ws_bytes": LL}
 
 
 def lib():

@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import guard as _guard
 from .env import gray_lut
 from .weights import BN_EPS, LAT_PAD_ELEMS, _pad8, init_state_dict, rep_layout, state_dict_spec
 
@@ -126,8 +127,14 @@ class Learner:
     """
 
     def __init__(self, mcfg, state_dict=None, K=5, dtype="f32", lr=None, seed=0, device="cuda", defer_wgrad=True,
-                 fuse_bn=True, streams=2, lat_rows=None, fuse_fin=None):
+                 fuse_bn=True, streams=2, lat_rows=None, fuse_fin=None, guard=None):
         L.require_gpu()
+        # guard (a mzba.guard.StepGuard): the optimizer step watched on the device — gradient norm,
+        # clipping, the skip of a non-finite step, the step counter and the learning-rate schedule, all inside the
+        # minibatch, so a guarded capture replays without any per-step host input. None: the launches of before.
+        if guard is not None and not isinstance(guard, _guard.StepGuard):
+            raise ValueError("guard must be a mzba.guard.StepGuard or None")
+        self.guard = guard
         # streams=2: the prediction net of every unrolled step runs on a side stream, concurrently
         # with the dynamics chain (forward: prediction(h_k) beside dynamics(h_k); backward: all
         # prediction backwards beside the dynamics chain). Same launches, same per-stream order:
@@ -188,6 +195,8 @@ class Learner:
         self.smin, self.smax = float(mcfg["supports_min"]), float(mcfg["supports_max"])
         self._build_params()
         self.step_count = 0
+        if guard is not None:
+            self._guard_init()
         self.nbt = {k: 0 for k in self.bn_keys}
         self._zero = torch.zeros(max(self.c0, self.c1, 2 * self.hist, 64), device=self.device)
         self._lut = torch.from_numpy(gray_lut()).to(self.device)
@@ -246,6 +255,8 @@ class Learner:
             self.M1.zero_()
             self.M2.zero_()
             self.step_count = 0
+            if self.guard is not None:
+                self.guard_block.zero_()  # the device step counter and the skip count start over
 
     def state_dict(self):
         out = OrderedDict()
@@ -269,9 +280,13 @@ class Learner:
                      ["param_groups"][0])
         group["params"] = list(range(len(self.params)))
         state = {}
-        if self.step_count:
+        steps = self.step_count
+        if self.guard is not None:  # the steps Adam has applied (skipped minibatches are not among them)
+            steps = self.applied_steps()
+            group["lr"] = self.current_lr()
+        if steps:
             for i, (key, p) in enumerate(self.params.items()):
-                state[i] = {"step": torch.tensor(float(self.step_count)),
+                state[i] = {"step": torch.tensor(float(steps)),
                             "exp_avg": p.to_ref(self.M1[p.off:p.off + p.n].view(p.kshape)),
                             "exp_avg_sq": p.to_ref(self.M2[p.off:p.off + p.n].view(p.kshape))}
         return {"state": state, "param_groups": [group]}
@@ -292,8 +307,97 @@ class Learner:
             if len(steps) > 1:
                 raise ValueError("optimizer state holds different step counts per parameter")
             self.step_count = steps.pop() if steps else 0
-            if d.get("param_groups"):
+            g = self.guard
+            if g is not None:  # seed the device counter; a scheduled / device lr is not the base rate lr0
+                self.guard_block[_guard.T_APPLIED_WORD] = self.step_count
+                self._graph = None  # a guarded graph holds the lr0 it was captured with
+            if d.get("param_groups") and (g is None or (g.lr_schedule is None and g.lr_dev is None)):
                 self.lr = float(d["param_groups"][0]["lr"])
+
+    # -- the step guard (csrc/guard.hip) ----------------------------------------------------------
+    def _guard_init(self):
+        """The guard's device state: the stats block, the reduction's scratch and the segment bounds (one per net:
+        state_dict_spec lays rep_net.*, dyn_net.* and pred_net.* out one after the other)."""
+        if L.lib().mzba_guard_block_bytes() != _guard.BLOCK_DT.itemsize:
+            raise RuntimeError("mzba.guard.BLOCK_DT does not match the library's mzba_guard_block")
+        self.guard_block = torch.zeros(_guard.BLOCK_WORDS, dtype=torch.int32, device=self.device)
+        self._g_ws = torch.empty(int(L.lib().mzba_grad_stats_ws_bytes(self.n_flat)), dtype=torch.uint8,
+                                 device=self.device)
+        self.guard_segments = ("rep_net", "dyn_net", "pred_net")
+        first, order = {}, []
+        for key, p in self.params.items():
+            net = key.split(".", 1)[0]
+            if net not in self.guard_segments:
+                raise ValueError(f"Learner guard: parameter {key} belongs to none of {self.guard_segments}")
+            if net not in first:
+                first[net] = p.off
+                order.append(net)
+            elif order[-1] != net:
+                raise ValueError(f"Learner guard: the parameters of {net} are not one contiguous run")
+        if tuple(order) != self.guard_segments:
+            raise ValueError(f"Learner guard: nets laid out as {order}, expected {self.guard_segments}")
+        bounds = [first[n] for n in self.guard_segments] + [self.n_flat]
+        bounds[0] = 0
+        self.guard_bounds = bounds
+        self._g_bounds = (ctypes.c_longlong * len(bounds))(*bounds)
+        self._g_tab = None
+
+    def _guard_table(self):
+        """The device pointer table of the running-statistics tensors and their snapshots; rebuilt when
+        load_state_dict has replaced the tensors (as RefreshTable.stale())."""
+        if self._g_tab is None or self._g_tab[2] is not self.run:
+            ts = [t for k in self.bn_keys for t in self.run[k]]
+            for t in ts:
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    raise ValueError("Learner guard: running statistics must be contiguous f32")
+            snap = torch.zeros(max(sum(t.numel() for t in ts), 1), dtype=torch.float32, device=self.device)
+            rec = np.zeros(len(ts), np.dtype([("live", "<u8"), ("snap", "<u8"), ("n", "<i4"), ("pad", "<i4")]))
+            off = 0
+            for r, t in zip(rec, ts):
+                r["live"], r["snap"], r["n"] = t.data_ptr(), snap.data_ptr() + 4 * off, t.numel()
+                off += t.numel()
+            tab = torch.from_numpy(rec.view(np.uint8).copy()).to(self.device) if len(ts) else snap.view(torch.uint8)
+            self._g_tab = ((tab, len(ts)), snap, self.run)
+        return self._g_tab[0]
+
+    def _guard_step(self, loss, s):
+        """The guarded optimizer step, eager and captured alike: the gradient's statistics, the decision and the
+        scalars of this step, Adam on the clipped gradient, the running statistics back if the step is skipped."""
+        g = self.guard
+        nseg = len(self.guard_segments)
+        L.call("mzba_grad_stats", L.ptr(self.G), self.n_flat, self._g_bounds, nseg, L.ptr(loss), L.ptr(self._g_ws),
+               self._g_ws.numel(), s)
+        rate, steps = g.lr_schedule[1:] if g.lr_schedule is not None else (1.0, 0)
+        L.call("mzba_guard_finish", L.ptr(self._g_ws), self._g_ws.numel(), self.n_flat, nseg, L.ptr(self.guard_block),
+               float("inf") if g.max_norm is None else g.max_norm, int(g.skip_nonfinite), self.lr, rate, steps,
+               L.ptr(g.lr_dev), BETAS[0], BETAS[1], ADAM_EPS, WEIGHT_DECAY, s)
+        L.call("mzba_adam_guard", L.ptr(self.P), L.ptr(self.G), L.ptr(self.M1), L.ptr(self.M2), self.n_flat,
+               L.ptr(self.guard_block), s)
+        tab, nt = self._guard_table()
+        L.call("mzba_guard_restore", L.ptr(tab), nt, L.ptr(self.guard_block), s)
+
+    def guard_stats(self):
+        """The stats block of the last guarded minibatch as a dict (one device-to-host copy, which synchronises)."""
+        if self.guard is None:
+            raise RuntimeError("Learner.guard_stats: this learner has no guard")
+        d = _guard.read_block(self.guard_block, len(self.guard_segments))
+        d["segments"] = list(self.guard_segments)
+        return d
+
+    def applied_steps(self):
+        """Optimizer steps applied (the device counter): step_count minus the skipped minibatches."""
+        if self.guard is None:
+            return self.step_count
+        return int(self.guard_block[_guard.T_APPLIED_WORD].item())
+
+    def current_lr(self):
+        """The learning rate the next optimizer step will use."""
+        g = self.guard
+        if g is not None and g.lr_dev is not None:
+            return float(g.lr_dev.item())
+        if g is not None and g.lr_schedule is not None:
+            return _guard.lr_at(self.lr, g.lr_schedule, self.applied_steps() + 1)
+        return self.lr
 
     def gradients(self):
         """Reference-layout gradients of the last minibatch (param.grad after loss.backward())."""
@@ -821,7 +925,8 @@ class Learner:
                 slots.numel() == self._g_slots.numel():
             self._g_slots.copy_(slots.to(device=self.device, dtype=torch.int32))
             self.step_count += 1
-            self._adam_sc.copy_(torch.tensor(self._adam_scalars(self.step_count), dtype=torch.float32))
+            if self.guard is None:  # a guarded graph computes its scalars itself
+                self._adam_sc.copy_(torch.tensor(self._adam_scalars(self.step_count), dtype=torch.float32))
             self._graph.replay()
             for k, d in self._nbt_step.items():
                 self.nbt[k] += d
@@ -850,6 +955,8 @@ class Learner:
         self._g_prio, self._g_seed = bool(prioritized), int(seed)
         self._g_slots = torch.zeros(B, dtype=torch.int32, device=self.device)
         self._adam_sc = torch.zeros(7, dtype=torch.float32, device=self.device)
+        if self.guard is not None:
+            self._guard_table()  # built (an upload) outside the capture; the guarded graph never reads _adam_sc
         if prioritized:
             # the sampler's step on the device, advanced inside the graph; _g_step_host is what it holds
             self._g_step = torch.full((1,), self.per_step, dtype=torch.int32, device=self.device)
@@ -883,7 +990,8 @@ class Learner:
         if self._graph is not None and self._g_prio and ring is self._g_ring and B == self._g_slots.numel() and \
                 int(seed) == self._g_seed:
             self.step_count += 1
-            self._adam_sc.copy_(torch.tensor(self._adam_scalars(self.step_count), dtype=torch.float32))
+            if self.guard is None:
+                self._adam_sc.copy_(torch.tensor(self._adam_scalars(self.step_count), dtype=torch.float32))
             if self._g_step_host != self.per_step:  # eager steps were taken since the last replay
                 self._g_step.fill_(self.per_step)
             self._graph.replay()
@@ -900,7 +1008,10 @@ class Learner:
     def _prioritized_body(self, ring, B, seed, step_dev):
         slots, weights, _ = ring.sample(B, self.per_step, seed=seed, step_dev=step_dev)
         loss = self._minibatch(ring, slots, weights)
-        ring.update_priorities(slots, self.last_td)
+        if self.guard is None:
+            ring.update_priorities(slots, self.last_td)
+        else:  # a skipped step leaves the priorities alone
+            ring.update_priorities(slots, self.last_td, guard_block=self.guard_block)
         self.last_slots, self.last_weights = slots, weights
         return loss
 
@@ -931,6 +1042,9 @@ class Learner:
         self._pending = {} if self.defer_wgrad else None
         self._owed = {}
         self._ctr_i = 0
+        if self.guard is not None:  # the running statistics as they stand: a skipped step puts them back
+            tab, nt = self._guard_table()
+            L.call("mzba_guard_snapshot", L.ptr(tab), nt, s)
         self._prepare_packs()
         # ---- forward (_k_step_rollout)
         cin_p = self.rep[0][1].cin_p
@@ -1007,7 +1121,9 @@ class Learner:
         self._join()
         # ---- Adam (networks.py:268)
         self.step_count += 1
-        if self._capturing:
+        if self.guard is not None:
+            self._guard_step(loss, s)
+        elif self._capturing:
             L.call("mzba_adam_dev", L.ptr(self.P), L.ptr(self.G), L.ptr(self.M1), L.ptr(self.M2), self.n_flat,
                    L.ptr(self._adam_sc), s)
         else:

@@ -222,13 +222,18 @@ class DeviceReplayBuffer:
                ws.numel(), L.stream())
         return slots, weights, probs
 
-    def update_priorities(self, slots, td):
+    def update_priorities(self, slots, td, guard_block=None):
         """q[slots[j]] = (td[j] + prio_eps) ** alpha (td: the learner's last_td for the windows `slots` of a
-        `sample`). No ingest may run between the sample and this call; duplicates must carry equal td."""
+        `sample`). No ingest may run between the sample and this call; duplicates must carry equal td.
+        guard_block (a guarded Learner's device stats block): q stays as it is when that step was skipped."""
         self._need_prio()
         if slots.dtype != torch.int32 or td.dtype != torch.float32 or slots.numel() != td.numel():
             raise ValueError("update_priorities takes i32 slots and f32 td of one length")
         slots, td = slots.contiguous(), td.contiguous()  # held until the launch is made
+        if guard_block is not None:
+            L.call("mzba_replay_priority_update_g", L.ptr(self._q), L.ptr(slots), L.ptr(td), slots.numel(),
+                   self.max_length, self.alpha, self.prio_eps, L.ptr(guard_block), L.stream())
+            return
         L.call("mzba_replay_priority_update", L.ptr(self._q), L.ptr(slots), L.ptr(td), slots.numel(), self.max_length,
                self.alpha, self.prio_eps, L.stream())
 
