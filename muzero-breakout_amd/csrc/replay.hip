@@ -185,8 +185,9 @@ int mzba_replay_write(const uint8_t* action, const float* reward, const uint8_t*
 
 int mzba_replay_states(const uint8_t* states, const int32_t* slots, int n, const float* lut8, float* out, int hist,
                        int HW, hipStream_t stream) {
-  MZ_CHECK_ARG(states && slots && lut8 && out && n >= 0 && hist > 0 && (hist * HW) % 4 == 0, -1);
-  if (n == 0) return 0;
+  MZ_CHECK_ARG(states && lut8 && n >= 0 && hist > 0 && (hist * HW) % 4 == 0, -1);
+  if (n == 0) return 0;  // an empty batch: its slots and out tensors have no storage, so no pointers
+  MZ_CHECK_ARG(slots && out, -1);
   hipLaunchKernelGGL(replay_states_kernel, dim3(n), dim3(256), 0, stream, states, slots, lut8, out, hist, HW);
   MZ_LAUNCH_CHECK();
   return 0;
