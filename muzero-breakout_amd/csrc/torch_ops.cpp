@@ -214,8 +214,10 @@ at::Tensor support_decode(const at::Tensor& logits, double smin, double smax) {
   check_dev(logits, "logits", at::kFloat);
   TORCH_CHECK(logits.dim() >= 1, "mz::support_decode: logits [..., n_supports]");
   const int n = (int)logits.size(-1);
+  TORCH_CHECK(n >= 2 && n <= 16, "mz::support_decode: 2 to 16 supports, got ", n);
   const int B = (int)(logits.numel() / n);
   at::Tensor out = at::empty(logits.sizes().slice(0, logits.dim() - 1), logits.options());
+  if (B == 0) return out;  // no rows: the empty result, as the reference's torch ops give (no launch)
   check_rc(mzba_support_decode(logits.data_ptr<float>(), out.data_ptr<float>(), B, n, (float)smin, (float)smax,
                                cur_stream(logits)),
            "mzba_support_decode");
