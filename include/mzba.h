@@ -50,6 +50,19 @@ int mzba_env_reset_compact(int32_t* paddle, int32_t* bx, int32_t* by, int32_t* d
                            int brick_rows, uint64_t seed, int episode, int env_offset, const int32_t* params,
                            int pad_action, hipStream_t stream);
 
+/* Streaming acting: launched at the head of acting step t = ctx[2], before the rep input is built.
+ * Every env with done != 0 or hist_len >= blk[1] (the per-episode record cap) is reset in place exactly as
+ * mzba_env_reset_compact resets it under the episode key blk[0] + t (blk: device int32[2] = {ep_base, cap}, so one
+ * captured graph serves every stage); the other envs are left as they are. start: u32 [T][B], row t is written:
+ * 0 = no episode of env b starts at row t, else bit 31 | paddle | bx << 10 | by << 20 of s0 (g(s0) can be rendered
+ * from the word alone). At t == 0 nothing is reset and every env's word is written from its current state (the state
+ * the stage's mzba_env_reset_compact left). H, W <= 256. */
+int mzba_env_restart_compact(int32_t* paddle, int32_t* bx, int32_t* by, int32_t* dx, float* dy, uint8_t* done,
+                             uint64_t* bricks, int nw, uint8_t* cur_frame, uint8_t* cur_src, uint8_t* hist_frames,
+                             uint8_t* hist_actions, int32_t* hist_len, int L, uint32_t* start, const int32_t* ctx,
+                             const int32_t* blk, int B, int H, int W, int paddle_width, int brick_rows, uint64_t seed,
+                             int env_offset, const int32_t* params, int pad_action, hipStream_t stream);
+
 /* One acting-loop env step (train_torch.py:201-209): step, render the u8 gray frame, push
  * (action, frame) into the history ring when the env is recorded (not prev_done; at the first
  * step prev_done aliases done, :179), and write the trajectory-sink row (rec_* may be NULL).
@@ -273,6 +286,27 @@ int mzba_replay_write(const uint8_t* action, const float* reward, const uint8_t*
                       int K, int hist, const float* dpow, hipStream_t stream);
 int mzba_replay_states(const uint8_t* states, const int32_t* slots, int n, const float* lut8, float* out, int hist,
                        int HW, hipStream_t stream);
+
+/* Streamed sinks (mzba_env_restart_compact: several episodes per env). A segment is env b's rows from a non-zero
+ * start word start[t][b] (u32 [T][B]) up to the row before the next one, or up to T; its records are its masked rows.
+ * The last segment of an env is closed iff done[b] || hlen[b] >= cap_len (both read at the end of the stage); an open
+ * one is kept only with keep_tail != 0. Kept segments: length > min_len and >= K, ordered by env, then start row.
+ * stream_plan (three launches: per-env count, scan, per-env fill): cnt i32 [B][2], offs i32 [B + 1][2] = exclusive
+ *   scans of the envs' (kept segments, windows), offs[B] = the totals (the ingest's one host read); table i32
+ *   [6][nmax + 1]: per kept segment env, start row, length, reward sum (f32 bits), start word, window offset
+ *   (entry [segments] = windows). nmax >= B * (T / max(min_len + 1, K)) or -2.
+ * stream_write: mzba_replay_write for the table's windows: records from the segment's start row on, the 31 pad frames
+ *   g(s0) rendered from the start word (H, W <= 256, paddle_width, brick_rows as in the env). Same ring rows,
+ *   arithmetic and eviction rule. */
+int mzba_replay_stream_plan(const float* reward, const uint8_t* mask, const uint32_t* start, const uint8_t* done,
+                            const int32_t* hlen, int T, int B, int K, int min_len, int cap_len, int keep_tail,
+                            int32_t* cnt, int32_t* offs, int32_t* table, int nmax, hipStream_t stream);
+int mzba_replay_stream_write(const uint8_t* action, const float* reward, const int64_t* counts, const float* value,
+                             const uint8_t* frame, int T, int B, int H, int W, int paddle_width, int brick_rows,
+                             const int32_t* table, int nmax, int n_segments, int n_windows, int64_t* past_actions,
+                             int64_t* future_actions, uint8_t* states, float* rewards, float* counts_out,
+                             float* values_out, float* targets, float* reward_sum, int cap, int head, int K, int hist,
+                             const float* dpow, hipStream_t stream);
 
 /* ===================== prioritized replay (MuZero, Appendix G; csrc/replay_prio.hip)
  * q f32[cap], 16-byte aligned, in slot space: q[slot] = p^alpha for a live window, exactly 0 for a slot that

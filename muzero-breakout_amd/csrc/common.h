@@ -112,6 +112,36 @@ MZ_DEV int mz_randbelow(uint32_t env, uint32_t stream, uint32_t step, uint32_t c
   return (int)((x * (uint64_t)n) >> 24);
 }
 
+// ------------------------------------------------------------------ g(s0) and the streaming start word
+// s0 (parallel_breakout.py:107-139) is the full brick rows, the paddle at column `paddle` of the last row and the ball
+// at (by, bx); its gray code at pixel p (bit0 paddle, bit1 ball, bit2 brick) needs no division. One function for the
+// reset kernel, the streaming restart kernel (env.hip) and the segmented ingest (replay.hip).
+MZ_DEV uint8_t mz_s0_code(int p, int H, int W, int pw, int brick_rows, int paddle, int bx, int by) {
+  const int q = p - ((H - 1) * W + paddle);
+  return (uint8_t)((q >= 0 && q < pw ? 1 : 0) | (p == by * W + bx ? 2 : 0) | (p < brick_rows * W ? 4 : 0));
+}
+// 16 consecutive pixels of g(s0) from p0 on (p0 % 16 == 0, H * W % 16 == 0)
+MZ_DEV uint4 mz_s0_chunk(int p0, int H, int W, int pw, int brick_rows, int paddle, int bx, int by) {
+  uint32_t w[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    w[q] = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      w[q] |= (uint32_t)mz_s0_code(p0 + 4 * q + k, H, W, pw, brick_rows, paddle, bx, by) << (8 * k);
+  }
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+// start word of a streamed sink row (include/mzba.h): 0 = no episode starts here, else bit 31 + s0's
+// (paddle, bx, by) in 10 bits each (all < 1024: H, W <= 256 is checked by the launchers)
+#define MZ_START_FLAG 0x80000000u
+MZ_DEV uint32_t mz_start_word(int paddle, int bx, int by) {
+  return MZ_START_FLAG | (uint32_t)paddle | ((uint32_t)bx << 10) | ((uint32_t)by << 20);
+}
+MZ_DEV void mz_start_unpack(uint32_t w, int& paddle, int& bx, int& by) {
+  paddle = (int)(w & 1023u); bx = (int)((w >> 10) & 1023u); by = (int)((w >> 20) & 1023u);
+}
+
 // ScalarTransforms.inverted_softmax_expectation (utils.py:74-81) for n <= 16 logits: softmax,
 // expectation over torch.linspace(smin, smax, n), then the reference's inverse transform.
 MZ_DEV float decode_support(const float* l, int n, float smin, float smax) {

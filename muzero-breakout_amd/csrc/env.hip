@@ -13,11 +13,8 @@ namespace {
 
 struct RewardCfg { float paddle_hit, brick_hit, lost, won; };
 
-// gray code of a pixel: bit0 paddle, bit1 ball, bit2 brick. The float value of a code is
-// clamp((0.3f*p + 1.0f*b) + 0.6f*br, 0, 1) (train_torch.py:334-358), see gray_lut().
-MZ_DEV uint8_t gray_code(bool paddle, bool ball, bool brick) {
-  return (uint8_t)((paddle ? 1 : 0) | (ball ? 2 : 0) | (brick ? 4 : 0));
-}
+// gray code of a pixel (mz_s0_code in common.h, the step kernel's render): bit0 paddle, bit1 ball, bit2 brick. The
+// float value of a code is clamp((0.3f*p + 1.0f*b) + 0.6f*br, 0, 1) (train_torch.py:334-358), see gray_lut().
 
 // ---------------------------------------------------------------- reset (planes)
 __device__ void reset_params(int b, int B, int W, int pw, uint64_t seed, int episode, int env_offset,
@@ -205,12 +202,65 @@ __global__ void env_reset_compact_kernel(Compact cs, uint8_t* __restrict__ cur_f
   }
   uint8_t* cf = cur_frame + (size_t)b * HW;
   for (int p = threadIdx.x; p < HW; p += blockDim.x) {
-    int y = p / W, x = p - y * W;
-    uint8_t c = gray_code(y == H - 1 && x >= ppos && x < ppos + pw, y == by && x == col, y < brick_rows);
+    uint8_t c = mz_s0_code(p, H, W, pw, brick_rows, ppos, col, by);
     if (!hist.cur_src) cf[p] = c;
     for (int k = 0; k < hist.L - 1; ++k) hist.frames[((size_t)b * (hist.L - 1) + k) * HW + p] = c;
   }
   for (int k = threadIdx.x; k < hist.L; k += blockDim.x) hist.actions[(size_t)b * hist.L + k] = (uint8_t)pad_action;
+}
+
+// Streaming restart (streaming acting): at the head of acting step t = ctx[2] every env that is done, or
+// whose episode holds blk[1] = cap records, starts a new episode in place, exactly as env_reset_compact_kernel would
+// reset it under the episode key blk[0] + t (ep_base + t). start[t][b] gets the env's start word (common.h): 0 when
+// no episode starts at row t, else s0's (paddle, bx, by); at t == 0 every env's, from the state the stage's reset
+// left. RE envs per block: a lane reads its env's two flags (coalesced), the restarting envs (about B / 30 a step)
+// are listed in LDS and the block renders their L - 1 pad frames with 16-B stores.
+constexpr int RE = 64;
+__global__ __launch_bounds__(256) void env_restart_compact_kernel(
+    Compact cs, uint8_t* __restrict__ cur_frame, History hist, uint32_t* __restrict__ start,
+    const int32_t* __restrict__ ctx, const int32_t* __restrict__ blk, int pad_action, int B, int H, int W, int pw,
+    int brick_rows, uint64_t seed, int env_offset, const int32_t* __restrict__ params) {
+  __shared__ int s_n, s_env[RE], s_paddle[RE], s_bx[RE], s_by[RE];
+  const int t = threadIdx.x;
+  const int row = ctx[2], ep_base = blk[0], cap = blk[1];
+  if (t == 0) s_n = 0;
+  __syncthreads();
+  const int b = blockIdx.x * RE + t;
+  if (t < RE && b < B) {
+    uint32_t word = 0;
+    if (row == 0) {
+      word = mz_start_word(cs.paddle[b], cs.bx[b], cs.by[b]);
+    } else if (cs.done[b] != 0 || hist.hlen[b] >= cap) {
+      int off, col, r0, dx;
+      reset_params(b, B, W, pw, seed, ep_base + row, env_offset, params, off, col, r0, dx);
+      const int ppos = W / 2 - pw / 2 + off;
+      const int by = ((H + r0) % H + H) % H;
+      cs.paddle[b] = ppos; cs.bx[b] = col; cs.by[b] = by; cs.dx[b] = dx; cs.dy[b] = -1.0f; cs.done[b] = 0;
+      hist.hlen[b] = 0;
+      if (hist.cur_src) hist.cur_src[b] = 1;
+      for (int w = 0; w < cs.nw; ++w) {
+        const int nbits = brick_rows * W - w * 64;
+        cs.bricks[(size_t)b * cs.nw + w] = nbits >= 64 ? ~0ull : (nbits > 0 ? (1ull << nbits) - 1ull : 0ull);
+      }
+      word = mz_start_word(ppos, col, by);
+      const int i = atomicAdd(&s_n, 1);
+      s_env[i] = b; s_paddle[i] = ppos; s_bx[i] = col; s_by[i] = by;
+    }
+    start[(size_t)row * B + b] = word;
+  }
+  __syncthreads();
+  const int n = s_n;
+  if (n == 0) return;
+  const int HW = H * W, chunks = HW / 16, L1 = hist.L - 1;
+  for (int i = t; i < n * hist.L; i += 256) hist.actions[(size_t)s_env[i / hist.L] * hist.L + i % hist.L] = (uint8_t)pad_action;
+  const int per = chunks * (hist.cur_src ? L1 : L1 + 1);  // slot L1 = cur_frame (double-write mode)
+  for (int i = t; i < n * per; i += 256) {
+    const int e = i / per, rem = i - e * per, k = rem / chunks, c = rem - k * chunks;
+    const uint4 v = mz_s0_chunk(c * 16, H, W, pw, brick_rows, s_paddle[e], s_bx[e], s_by[e]);
+    const size_t gb = (size_t)s_env[e];
+    uint8_t* dst = k < L1 ? hist.frames + (gb * L1 + k) * HW : cur_frame + gb * HW;
+    *reinterpret_cast<uint4*>(dst + c * 16) = v;
+  }
 }
 
 // one 16-B chunk of a rendered frame: a non-temporal store (written once, read by a later launch
@@ -370,7 +420,7 @@ __global__ __launch_bounds__(256, 8) void env_step_compact_kernel(
       const uint32_t nb = ((brk16 >> (4 * q)) & 15u) * 0x204081u & 0x01010101u;
       const uint32_t nl = ((ball16 >> (4 * q)) & 15u) * 0x204081u & 0x01010101u;
       const uint32_t np = ((pad16 >> (4 * q)) & 15u) * 0x204081u & 0x01010101u;
-      wv[q] = (nb << 2) | (nl << 1) | np;  // gray_code(paddle, ball, brick)
+      wv[q] = (nb << 2) | (nl << 1) | np;  // the gray code: bit0 paddle, bit1 ball, bit2 brick
     }
     uint4 v = make_uint4(wv[0], wv[1], wv[2], wv[3]);
     if (sink_frame) frame_store(sink_frame + (size_t)gb * HW + c * 16, v);
@@ -523,6 +573,21 @@ int mzba_env_reset_compact(int32_t* paddle, int32_t* bx, int32_t* by, int32_t* d
   History h{hist_frames, hist_actions, hist_len, L, cur_src};
   hipLaunchKernelGGL(env_reset_compact_kernel, dim3(B), dim3(256), 0, stream, cs, cur_frame, h, pad_action, B, H, W,
                      paddle_width, brick_rows, seed, episode, env_offset, params);
+  MZ_LAUNCH_CHECK();
+  return 0;
+}
+
+int mzba_env_restart_compact(int32_t* paddle, int32_t* bx, int32_t* by, int32_t* dx, float* dy, uint8_t* done,
+                             uint64_t* bricks, int nw, uint8_t* cur_frame, uint8_t* cur_src, uint8_t* hist_frames,
+                             uint8_t* hist_actions, int32_t* hist_len, int L, uint32_t* start, const int32_t* ctx,
+                             const int32_t* blk, int B, int H, int W, int paddle_width, int brick_rows, uint64_t seed,
+                             int env_offset, const int32_t* params, int pad_action, hipStream_t stream) {
+  MZ_CHECK_ARG(B > 0 && L >= 2 && nw >= 1 && nw * 64 >= brick_rows * W && nw <= 4 && (H * W) % 16 == 0 && H <= 256 &&
+               W <= 256 && pad_action >= 0 && pad_action < 3 && start && ctx && blk, -1);
+  Compact cs{paddle, bx, by, dx, dy, done, bricks, nw};
+  History h{hist_frames, hist_actions, hist_len, L, cur_src};
+  hipLaunchKernelGGL(env_restart_compact_kernel, dim3((B + RE - 1) / RE), dim3(256), 0, stream, cs, cur_frame, h, start,
+                     ctx, blk, pad_action, B, H, W, paddle_width, brick_rows, seed, env_offset, params);
   MZ_LAUNCH_CHECK();
   return 0;
 }

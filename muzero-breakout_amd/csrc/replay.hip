@@ -11,6 +11,8 @@
 //   replay_write_kernel (one workgroup per surviving window): writes the window into a FIFO ring
 //                        of fixed-size rows (frames stay u8 codes: 10 KB per window at 16x20);
 //   replay_states_kernel: gathers a batch of windows' frames as f32 grayscale (the learner's input).
+// A streamed sink (several episodes per env) goes through stream_count / stream_scan / stream_fill
+// (a flat segment table) and stream_write_kernel, which shares write_window with replay_write_kernel.
 #include "common.h"
 
 namespace {
@@ -82,6 +84,48 @@ __global__ __launch_bounds__(PT) void replay_plan_kernel(ReplayRecords r, int K,
   if (tid == PT - 1) offsets[r.B] = part[PT - 1];
 }
 
+// window s of a trajectory of L records whose first record is sink row t0 of env b -> ring row `slot`;
+// frame0_chunk(q) = 16-B chunk q of the trajectory's g(s0)
+template <typename F0>
+MZ_DEV void write_window(const ReplayRecords& r, const ReplayRing& g, int b, int t0, int s, int L, float rsum,
+                         size_t slot, int K, int hist, const float* __restrict__ dpow, F0 frame0_chunk) {
+  const int tid = threadIdx.x;
+  const size_t B = r.B;
+  if (tid < hist) {  // actions[s + tid] of the padded list: 32 zeros, then the records
+    const int i = s + tid;
+    g.past_actions[slot * hist + tid] = i < hist ? 0 : (int64_t)r.action[(size_t)(t0 + i - hist) * B + b];
+  } else if (tid < hist + K) {
+    const int i = tid - hist, t = t0 + s + i;  // records [s, s + K) (the padded lists' [s + 32, s + 32 + K))
+    g.future_actions[slot * K + i] = (int64_t)r.action[(size_t)t * B + b];
+    g.rewards[slot * K + i] = r.reward[(size_t)t * B + b];
+    g.values[slot * K + i] = r.value[(size_t)t * B + b];
+    for (int a = 0; a < 3; ++a) g.counts[(slot * K + i) * 3 + a] = (float)r.counts[((size_t)t * B + b) * 3 + a];
+    // n-step target (replay_buffer.py:137-151): bootstrap td_steps = 10 ahead, scaled by
+    // discount**K; dpow[k] = f32(discount**k) (python double pow, host table), dpow[T + 1] = f32(discount**K)
+    const int cur = s + i, boot = s + 10 + i;
+    float v;
+    if (boot < L) {
+      v = r.value[(size_t)(t0 + boot) * B + b] * dpow[r.T + 1];
+      for (int k = 0; k < boot - cur; ++k) v = v + dpow[k] * r.reward[(size_t)(t0 + cur + k) * B + b];
+    } else {
+      v = dpow[0] * r.reward[(size_t)(t0 + cur) * B + b];  // python 0.0 + the first term is that term
+      for (int k = 1; k < L - cur; ++k) v = v + dpow[k] * r.reward[(size_t)(t0 + cur + k) * B + b];
+    }
+    g.targets[slot * K + i] = v;
+  } else if (tid == hist + K) {
+    g.reward_sum[slot] = rsum;
+  }
+  // frames: the padded states list = 31 x g(s0), then the recorded frames
+  const int chunks = r.HW / 16;
+  uint8_t* dst = g.states + slot * hist * r.HW;
+  for (int c = tid; c < hist * chunks; c += 256) {
+    const int f = c / chunks, q = c - f * chunks, i = s + f;
+    const uint4 v = i < hist - 1 ? frame0_chunk(q)
+                                 : *reinterpret_cast<const uint4*>(r.frame + ((size_t)(t0 + i - (hist - 1)) * B + b) * r.HW + q * 16);
+    *reinterpret_cast<uint4*>(dst + (size_t)f * r.HW + q * 16) = v;
+  }
+}
+
 // one workgroup per window j in [j0, n): env by binary search of offsets, ring slot (head + j) % cap
 __global__ __launch_bounds__(256) void replay_write_kernel(ReplayRecords r, ReplayRing g, const int32_t* __restrict__ lens,
                                                            const float* __restrict__ rsum,
@@ -93,42 +137,123 @@ __global__ __launch_bounds__(256) void replay_write_kernel(ReplayRecords r, Repl
     const int mid = (lo + hi) >> 1;
     if (offsets[mid] <= j) lo = mid; else hi = mid;
   }
-  const int b = lo, s = j - offsets[b], L = lens[b];
-  const size_t slot = ((size_t)head + j) % g.cap;
-  const int tid = threadIdx.x;
-  const size_t B = r.B;
-  if (tid < hist) {  // actions[s + tid] of the padded list: 32 zeros, then the records
-    const int i = s + tid;
-    g.past_actions[slot * hist + tid] = i < hist ? 0 : (int64_t)r.action[(size_t)(i - hist) * B + b];
-  } else if (tid < hist + K) {
-    const int i = tid - hist, t = s + i;  // records [s, s + K) (the padded lists' [s + 32, s + 32 + K))
-    g.future_actions[slot * K + i] = (int64_t)r.action[(size_t)t * B + b];
-    g.rewards[slot * K + i] = r.reward[(size_t)t * B + b];
-    g.values[slot * K + i] = r.value[(size_t)t * B + b];
-    for (int a = 0; a < 3; ++a) g.counts[(slot * K + i) * 3 + a] = (float)r.counts[((size_t)t * B + b) * 3 + a];
-    // n-step target (replay_buffer.py:137-151): bootstrap td_steps = 10 ahead, scaled by
-    // discount**K; dpow[k] = f32(discount**k) (python double pow, host table), dpow[T + 1] = f32(discount**K)
-    const int cur = s + i, boot = s + 10 + i;
-    float v;
-    if (boot < L) {
-      v = r.value[(size_t)boot * B + b] * dpow[r.T + 1];
-      for (int k = 0; k < boot - cur; ++k) v = v + dpow[k] * r.reward[(size_t)(cur + k) * B + b];
-    } else {
-      v = dpow[0] * r.reward[(size_t)cur * B + b];  // python 0.0 + the first term is that term
-      for (int k = 1; k < L - cur; ++k) v = v + dpow[k] * r.reward[(size_t)(cur + k) * B + b];
+  const int b = lo;
+  const uint8_t* f0 = r.frame0 + (size_t)b * r.HW;
+  write_window(r, g, b, 0, j - offsets[b], lens[b], rsum[b], ((size_t)head + j) % g.cap, K, hist, dpow,
+               [f0](int q) { return *reinterpret_cast<const uint4*>(f0 + q * 16); });
+}
+
+// ---------------------------------------------------------------- streamed sinks (streaming acting)
+// A streamed sink holds several episodes per env: a segment is env b's rows from a non-zero start word (common.h) up
+// to the row before the next one, or up to T; its records are the masked rows (a prefix). The last segment of an env
+// is closed iff done[b] || hlen[b] >= cap_len at the end of the stage; an open one is kept only with keep_tail. Kept
+// segments (the length rule of replay_plan_kernel) are ordered by env, then by start row.
+struct StreamPlan {
+  const uint32_t* start;  // [T][B]
+  const uint8_t* done;    // [B] at the end of the stage
+  const int32_t* hlen;    // [B]
+  int cap_len, keep_tail, K, min_len;
+};
+
+// f(t0, L, reward sum, start word) for every kept segment of env b, in row order
+template <typename F>
+MZ_DEV void for_each_kept_segment(const ReplayRecords& r, const StreamPlan& p, int b, F f) {
+  int t0 = -1, L = 0;
+  float s = 0.f;
+  uint32_t w0 = 0;
+  for (int t = 0; t < r.T; ++t) {  // lanes of a wave read consecutive envs of row t
+    const size_t i = (size_t)t * r.B + b;
+    const uint32_t w = p.start[i];
+    if (w) {
+      if (t0 >= 0 && L > p.min_len && L >= p.K) f(t0, L, s, w0);
+      t0 = t; L = 0; s = 0.f; w0 = w;
     }
-    g.targets[slot * K + i] = v;
-  } else if (tid == hist + K) {
-    g.reward_sum[slot] = rsum[b];
+    if (t0 >= 0 && r.mask[i]) {
+      s = s + r.reward[i];  // ObservationTrajectory.reward_sum (replay_buffer.py:34)
+      ++L;
+    }
   }
-  // frames: the padded states list = 31 x g(s0), then the recorded frames
-  const int chunks = r.HW / 16;
-  uint8_t* dst = g.states + slot * hist * r.HW;
-  for (int c = tid; c < hist * chunks; c += 256) {
-    const int f = c / chunks, q = c - f * chunks, i = s + f;
-    const uint8_t* src = i < hist - 1 ? r.frame0 + (size_t)b * r.HW : r.frame + ((size_t)(i - (hist - 1)) * B + b) * r.HW;
-    *reinterpret_cast<uint4*>(dst + (size_t)f * r.HW + q * 16) = *reinterpret_cast<const uint4*>(src + q * 16);
+  const bool closed = p.done[b] != 0 || p.hlen[b] >= p.cap_len;
+  if (t0 >= 0 && (closed || p.keep_tail) && L > p.min_len && L >= p.K) f(t0, L, s, w0);
+}
+
+// one thread per env: cnt[b] = (kept segments, their windows)
+__global__ __launch_bounds__(256) void stream_count_kernel(ReplayRecords r, StreamPlan p, int32_t* __restrict__ cnt) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= r.B) return;
+  int ns = 0, nw = 0;
+  for_each_kept_segment(r, p, b, [&](int, int L, float, uint32_t) { ++ns; nw += L - p.K + 1; });
+  cnt[2 * b] = ns; cnt[2 * b + 1] = nw;
+}
+
+// one workgroup: offs[b] = exclusive scan of cnt over the envs (both columns), offs[B] = the totals
+__global__ __launch_bounds__(PT) void stream_scan_kernel(const int32_t* __restrict__ cnt, int32_t* __restrict__ offs, int B) {
+  __shared__ int32_t ps[PT], pw[PT];
+  const int tid = threadIdx.x;
+  const int per = (B + PT - 1) / PT;
+  int ms = 0, mw = 0;
+  for (int u = 0; u < per; ++u) {
+    const int b = tid * per + u;
+    if (b >= B) break;
+    ms += cnt[2 * b]; mw += cnt[2 * b + 1];
   }
+  ps[tid] = ms; pw[tid] = mw;
+  __syncthreads();
+  for (int o = 1; o < PT; o <<= 1) {
+    const int vs = tid >= o ? ps[tid - o] : 0, vw = tid >= o ? pw[tid - o] : 0;
+    __syncthreads();
+    ps[tid] += vs; pw[tid] += vw;
+    __syncthreads();
+  }
+  int rs = ps[tid] - ms, rw = pw[tid] - mw;
+  for (int u = 0; u < per; ++u) {
+    const int b = tid * per + u;
+    if (b >= B) break;
+    offs[2 * b] = rs; offs[2 * b + 1] = rw;
+    rs += cnt[2 * b]; rw += cnt[2 * b + 1];
+  }
+  if (tid == PT - 1) { offs[2 * B] = ps[PT - 1]; offs[2 * B + 1] = pw[PT - 1]; }
+}
+
+// the flat segment table, six columns of nmax + 1 words: env, start row, length, reward sum (f32 bits), start word,
+// window offset (exclusive scan over the kept segments; entry [number of segments] = the number of windows)
+struct SegTable {
+  int32_t* w; int nmax;
+  MZ_DEV int32_t* col(int k) const { return w + (size_t)k * (nmax + 1); }
+};
+
+// one thread per env: its kept segments into the table from offs[b] on
+__global__ __launch_bounds__(256) void stream_fill_kernel(ReplayRecords r, StreamPlan p, const int32_t* __restrict__ offs,
+                                                          SegTable tb) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= r.B) return;
+  int si = offs[2 * b], wo = offs[2 * b + 1];
+  for_each_kept_segment(r, p, b, [&](int t0, int L, float s, uint32_t w0) {
+    if (si < tb.nmax) {
+      tb.col(0)[si] = b; tb.col(1)[si] = t0; tb.col(2)[si] = L; tb.col(3)[si] = __float_as_int(s);
+      tb.col(4)[si] = (int32_t)w0; tb.col(5)[si] = wo;
+    }
+    ++si; wo += L - p.K + 1;
+  });
+  if (b == r.B - 1 && si <= tb.nmax) tb.col(5)[si] = wo;
+}
+
+// one workgroup per window j in [j0, n): segment by binary search of the table's window offsets
+__global__ __launch_bounds__(256) void stream_write_kernel(ReplayRecords r, ReplayRing g, SegTable tb, int nseg, int H, int W,
+                                                           int pw, int brick_rows, int K, int hist,
+                                                           const float* __restrict__ dpow, int head, int j0) {
+  const int j = j0 + blockIdx.x;
+  const int32_t* woff = tb.col(5);
+  int lo = 0, hi = nseg;  // last segment with woff[seg] <= j
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (woff[mid] <= j) lo = mid; else hi = mid;
+  }
+  int paddle, bx, by;
+  mz_start_unpack((uint32_t)tb.col(4)[lo], paddle, bx, by);
+  write_window(r, g, tb.col(0)[lo], tb.col(1)[lo], j - woff[lo], tb.col(2)[lo], __int_as_float(tb.col(3)[lo]),
+               ((size_t)head + j) % g.cap, K, hist, dpow,
+               [=](int q) { return mz_s0_chunk(q * 16, H, W, pw, brick_rows, paddle, bx, by); });
 }
 
 // batch gather of window frames as f32 grayscale: out[n][hist][HW] = lut[code & 7]
@@ -179,6 +304,47 @@ int mzba_replay_write(const uint8_t* action, const float* reward, const uint8_t*
   const int j0 = n_windows > cap ? n_windows - cap : 0;  // older windows would be evicted at once
   hipLaunchKernelGGL(replay_write_kernel, dim3(n_windows - j0), dim3(256), 0, stream, r, g, lens, rsum, offsets, K,
                      hist, dpow, head, j0);
+  MZ_LAUNCH_CHECK();
+  return 0;
+}
+
+int mzba_replay_stream_plan(const float* reward, const uint8_t* mask, const uint32_t* start, const uint8_t* done,
+                            const int32_t* hlen, int T, int B, int K, int min_len, int cap_len, int keep_tail,
+                            int32_t* cnt, int32_t* offs, int32_t* table, int nmax, hipStream_t stream) {
+  MZ_CHECK_ARG(T > 0 && B > 0 && K > 0 && reward && mask && start && done && hlen && cnt && offs && table, -1);
+  // a kept segment holds at least max(min_len + 1, K) of its env's T rows
+  const int keep = (min_len + 1 > K ? min_len + 1 : K);
+  MZ_CHECK_ARG(nmax >= 0 && (long long)nmax >= (long long)B * (T / keep), -2);
+  ReplayRecords r{nullptr, reward, mask, nullptr, nullptr, nullptr, nullptr, T, B, 0};
+  StreamPlan p{start, done, hlen, cap_len, keep_tail, K, min_len};
+  SegTable tb{table, nmax};
+  const dim3 grid((B + 255) / 256);
+  hipLaunchKernelGGL(stream_count_kernel, grid, dim3(256), 0, stream, r, p, cnt);
+  hipLaunchKernelGGL(stream_scan_kernel, dim3(1), dim3(PT), 0, stream, cnt, offs, B);
+  hipLaunchKernelGGL(stream_fill_kernel, grid, dim3(256), 0, stream, r, p, offs, tb);
+  MZ_LAUNCH_CHECK();
+  return 0;
+}
+
+int mzba_replay_stream_write(const uint8_t* action, const float* reward, const int64_t* counts, const float* value,
+                             const uint8_t* frame, int T, int B, int H, int W, int paddle_width, int brick_rows,
+                             const int32_t* table, int nmax, int n_segments, int n_windows, int64_t* past_actions,
+                             int64_t* future_actions, uint8_t* states, float* rewards, float* counts_out,
+                             float* values_out, float* targets, float* reward_sum, int cap, int head, int K, int hist,
+                             const float* dpow, hipStream_t stream) {
+  MZ_CHECK_ARG(T > 0 && B > 0 && H > 0 && W > 0 && H <= 256 && W <= 256 && (H * W) % 16 == 0 && K > 0 && hist >= 2 &&
+               hist + K < 256 && cap > 0 && head >= 0 && head < cap && n_windows >= 0 && n_segments >= 0 &&
+               n_segments <= nmax && n_segments <= n_windows, -1);
+  MZ_CHECK_ARG(dpow && action && reward && counts && value && frame && table && past_actions && future_actions &&
+               states && rewards && counts_out && values_out && targets && reward_sum, -1);
+  if (n_windows == 0) return 0;
+  MZ_CHECK_ARG(n_segments > 0, -1);
+  ReplayRecords r{action, reward, nullptr, counts, value, frame, nullptr, T, B, H * W};
+  ReplayRing g{past_actions, future_actions, states, rewards, counts_out, values_out, targets, reward_sum, cap};
+  SegTable tb{const_cast<int32_t*>(table), nmax};
+  const int j0 = n_windows > cap ? n_windows - cap : 0;  // older windows would be evicted at once
+  hipLaunchKernelGGL(stream_write_kernel, dim3(n_windows - j0), dim3(256), 0, stream, r, g, tb, n_segments, H, W,
+                     paddle_width, brick_rows, K, hist, dpow, head, j0);
   MZ_LAUNCH_CHECK();
   return 0;
 }

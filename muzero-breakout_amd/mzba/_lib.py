@@ -65,6 +65,10 @@ SIGNATURES = {
     "mzba_replay_plan": [P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P],
     "mzba_replay_write": [P, P, P, P, P, P, P, I, I, I, P, P, P, I, P, P, P, P, P, P, P, P, I, I, I, I, P, P],
     "mzba_replay_states": [P, P, I, P, P, I, I, P],
+    # streaming acting (env.hip restart, replay.hip segmented ingest)
+    "mzba_env_restart_compact": [P, P, P, P, P, P, P, I, P, P, P, P, P, I, P, P, P, I, I, I, I, I, U64, I, P, I, P],
+    "mzba_replay_stream_plan": [P, P, P, P, P, I, I, I, I, I, I, P, P, P, I, P],
+    "mzba_replay_stream_write": [P, P, P, P, P, I, I, I, I, I, I, P, I, I, I, P, P, P, P, P, P, P, P, I, I, I, I, P, P],
     # prioritized replay (replay_prio.hip)
     "mzba_replay_priority_init": [P, P, P, I, I, I, I, F, F, P],
     "mzba_replay_priority_update": [P, P, P, I, I, F, F, P],

@@ -113,6 +113,9 @@ class ActingLoop:
         # steps then run eagerly
         self.inject_noise = None
         self._noise_in = None
+        # optional callable (loop): launched at the head of every acting step, ahead of the rep input
+        # (mzba.stream.StreamingStage restarts finished envs there); None: the lockstep launches
+        self.restart = None
         self.search_id = 0
         self.step_index = 0
         self.episode = 0
@@ -152,6 +155,8 @@ class ActingLoop:
         """One acting step, every launch stream-ordered and parameterised by self.ctx."""
         env, ws = self.env, self.ws
         n = ws.n
+        if self.restart is not None:
+            self.restart(self)
         # _prepare_mcts_input + create_hidden_state_root -> pool slot 0
         env.build_rep_input(self.rep_in, self.cs, self.agent.dtype == "bf16")
         self.rep_runner.representation(self.rep_in, ws.cur, pool=ws.pool, pool_env_stride=(ws.S + 1) * n)

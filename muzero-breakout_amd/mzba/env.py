@@ -165,6 +165,15 @@ class CompactBreakout:
                self.brick_rows, self.seed, episode, self.env_offset, L.ptr(pr), self.pad_action, L.stream())
         self.valid.fill_(1.0)
 
+    def restart(self, start, ctx, blk, params=None):
+        """Streaming acting: reset in place every env that is done or holds blk[1] records, under the
+        episode key blk[0] + ctx[2], and write row ctx[2] of `start` (u32 (T, B) start words as int32;
+        include/mzba.h). `params`: device int32 (4, B) in place of the keyed draws."""
+        L.call("mzba_env_restart_compact", *self._state_ptrs(), L.ptr(self.cur_frame), L.ptr(self.cur_src),
+               L.ptr(self.hist_frames), L.ptr(self.hist_actions), L.ptr(self.hist_len), self.Lh, L.ptr(start),
+               L.ptr(ctx), L.ptr(blk), self.B, self.H, self.W, self.pw, self.brick_rows, self.seed, self.env_offset,
+               L.ptr(params), self.pad_action, L.stream())
+
     def step(self, action, first_step, rec=None, t=0, ctx=None):
         """action: int64 (B,) device. rec: optional sink dict of (T,B,...) buffers, row t; with a
         device step context `ctx` the row (and first_step) are read on the device instead."""

@@ -2,7 +2,8 @@
 
 The windows the reference builds in a Python triple loop (`save_observation_trajectory`,
 replay_buffer.py:96-165) are built on the device (csrc/replay.hip) straight from the acting
-loop's sink (`ingest_records`) or from host `ObservationTrajectory` objects
+loop's sink (`ingest_records`; `ingest_stream` for a streamed stage's sink of several episodes per
+env) or from host `ObservationTrajectory` objects
 (`save_observation_trajectory`, same arithmetic). Storage is a FIFO ring of `max_length`
 fixed-size rows in HBM (frames as u8 gray codes, 10 KB per window at 16x20); the getters
 return device tensors with the reference's dtypes and shapes.
@@ -90,11 +91,53 @@ class DeviceReplayBuffer:
                L.ptr(g["future_actions"]), L.ptr(g["states"]), L.ptr(g["rewards"]), L.ptr(g["counts"]),
                L.ptr(g["values"]), L.ptr(g["targets"]), L.ptr(g["reward_sum"]), cap, head, self.K,
                self.hist_seq_len, L.ptr(self._powers(T)), L.stream())
+        self._commit(head, n)
+
+    def _commit(self, head, n):
+        """The ring's bookkeeping after n windows were written from slot `head` on (the newest max_length kept)."""
+        cap = self.max_length
         if self.prioritized:
             self._init_priorities(head, n)
         total = self.length + n
         self.length = min(total, cap)
         self.start = (self.start + total - self.length) % cap
+
+    def ingest_stream(self, rec, T, done, hlen, tail="drop", min_len=None, episode_cap=261, paddle_width=6,
+                      brick_rows=3):
+        """A streamed stage's sink (mzba.stream.StreamingStage): `rec` as for ingest_records plus rec["start"], the
+        (T_max, B) start words; `done` u8 [B] and `hlen` i32 [B] are the envs' flags at the end of the stage. A
+        segment (one env's rows from a start word up to the next one, or T) is a trajectory: pad frames g(s0)
+        rendered from its start word, then its records. An env's last segment is closed iff done[b] or hlen[b] >=
+        episode_cap; an open one is dropped (tail="drop") or ingested as a truncated trajectory (tail="keep"). Kept
+        segments (length > min_len, default K + 1, and >= K) are saved by env, then by start row, so a sink with
+        one closed segment per env fills the ring exactly as ingest_records does. One host read. -> windows."""
+        if tail not in ("drop", "keep"):
+            raise ValueError("tail must be 'drop' or 'keep'")
+        if rec.get("frame") is None or rec.get("start") is None:
+            raise ValueError("ingest_stream needs the sink's recorded frames and start words")
+        min_len = self.K + 1 if min_len is None else min_len
+        B = rec["action"].shape[1]
+        dev = self.device
+        nmax = B * (T // max(min_len + 1, self.K))
+        cnt = torch.empty(B, 2, dtype=torch.int32, device=dev)
+        offs = torch.empty(B + 1, 2, dtype=torch.int32, device=dev)
+        table = torch.empty(6, nmax + 1, dtype=torch.int32, device=dev)
+        L.call("mzba_replay_stream_plan", L.ptr(rec["reward"]), L.ptr(rec["mask"]), L.ptr(rec["start"]), L.ptr(done),
+               L.ptr(hlen), T, B, self.K, min_len, int(episode_cap), 1 if tail == "keep" else 0, L.ptr(cnt),
+               L.ptr(offs), L.ptr(table), nmax, L.stream())
+        nseg, n = offs[B].tolist()
+        cap = self.max_length
+        head = (self.start + self.length) % cap
+        g = self._ring
+        L.call("mzba_replay_stream_write", L.ptr(rec["action"]), L.ptr(rec["reward"]), L.ptr(rec["counts"]),
+               L.ptr(rec["values"]), L.ptr(rec["frame"]), T, B, self.H, self.W, paddle_width, brick_rows, L.ptr(table),
+               nmax, nseg, n, L.ptr(g["past_actions"]), L.ptr(g["future_actions"]), L.ptr(g["states"]),
+               L.ptr(g["rewards"]), L.ptr(g["counts"]), L.ptr(g["values"]), L.ptr(g["targets"]),
+               L.ptr(g["reward_sum"]), cap, head, self.K, self.hist_seq_len, L.ptr(self._powers(T)), L.stream())
+        self._commit(head, n)
+        # a segment of L records gives L - K + 1 windows: the kept rows are windows + segments * (K - 1)
+        self.last_stream = {"segments": nseg, "windows": n}
+        return n
 
     def save_observation_trajectory(self, observation_trajectory):
         """replay_buffer.py:96-165 for one host trajectory (padded as _pad_initial_state builds it)."""
