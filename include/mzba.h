@@ -35,20 +35,48 @@ int mzba_env_step_planes(const float* state, float* next_state, const int64_t* a
 /* RLSystem.convert_to_grayscale (train_torch.py:334-358): (B,3,H,W) -> (B,1,H,W) f32. */
 int mzba_grayscale_planes(const float* state, float* gray, int B, int H, int W, hipStream_t stream);
 
-/* Frame storage (reset / step / rep input / current frame): cur_src (u8[B], may be NULL) selects
- * single-write mode — a frame recorded into the history ring is not also copied to cur_frame;
- * cur_src[b] = 1 says env b's current frame is the ring's newest entry, 0 that it is cur_frame[b]
- * (a done env: history frozen, frame live). With cur_src = NULL cur_frame always holds it.
- * Compact env for the fused acting loop: same rules as mzba_env_step_planes on SoA scalars
- * (paddle col, ball x/y, dx, dy, done) + a brick bitmask (nw u64 words per env over the brick rows).
- * Reset also does _pad_initial_state (train_torch.py:313-332): frame-history ring filled with
- * g(s0) (L-1 frames of H*W u8 gray codes), action ring (L) filled with pad_action (0 for the acting
- * loop, 1 for run_test_simulation, train_torch.py:545), hist_len = 0. */
-int mzba_env_reset_compact(int32_t* paddle, int32_t* bx, int32_t* by, int32_t* dx, float* dy, uint8_t* done,
-                           uint64_t* bricks, int nw, uint8_t* cur_frame, uint8_t* cur_src, uint8_t* hist_frames,
-                           uint8_t* hist_actions, int32_t* hist_len, int L, int B, int H, int W, int paddle_width,
-                           int brick_rows, uint64_t seed, int episode, int env_offset, const int32_t* params,
-                           int pad_action, hipStream_t stream);
+/* Compact env for the fused acting loop: same rules as mzba_env_step_planes on SoA scalars + a brick bitmask, with
+ * the frame-history ring of _pad_initial_state / _prepare_mcts_input (train_torch.py:313-332, 259-293). One object,
+ * stated once; the entry points below read it on the host at call time (so every call stays graph-capturable).
+ * Frame storage: cur_src selects single-write mode — a frame recorded into the history ring is not also copied to
+ * cur_frame; cur_src[b] = 1 says env b's current frame is the ring's newest entry, 0 that it is cur_frame[b] (a done
+ * env: history frozen, frame live). With cur_src = NULL cur_frame always holds it. */
+typedef struct mzba_env_state {
+  int32_t* paddle;        /* i32 [B] paddle's left column */
+  int32_t* bx;            /* i32 [B] ball column */
+  int32_t* by;            /* i32 [B] ball row */
+  int32_t* dx;            /* i32 [B] */
+  float* dy;              /* f32 [B] */
+  uint8_t* done;          /* u8 [B] */
+  uint64_t* bricks;       /* u64 [B][nw] bitmask over the brick rows, bit = row * W + col */
+  int nw;                 /* words per env: 1 <= nw <= 4, nw * 64 >= brick_rows * W */
+  uint8_t* cur_frame;     /* u8 [B][H*W] gray codes */
+  uint8_t* cur_src;       /* u8 [B], may be NULL (see above) */
+  uint8_t* hist_frames;   /* u8 [B][L-1][H*W] frame ring */
+  uint8_t* hist_actions;  /* u8 [B][L] action ring */
+  int32_t* hist_len;      /* i32 [B] records pushed so far */
+  int L;                  /* history length, >= 2 */
+  int B, H, W, paddle_width, brick_rows;  /* (H * W) % 16 == 0 */
+} mzba_env_state;
+
+/* Trajectory sink of the acting loop (replay_buffer.py:17-35 ObservationTrajectory fields), T rows of B envs. A
+ * consumer that does not read a field accepts NULL there. */
+typedef struct mzba_sink {
+  uint8_t* action;        /* u8 [T][B] */
+  float* reward;          /* f32 [T][B] */
+  uint8_t* mask;          /* u8 [T][B] recorded (not prev_done) */
+  int64_t* counts;        /* i64 [T][B][3] visit counts */
+  float* values;          /* f32 [T][B] root values */
+  uint8_t* frame;         /* u8 [T][B][HW] gray codes */
+  uint32_t* start;        /* u32 [T][B] start words (streamed sinks, mzba_env_restart_compact) */
+  int T, B, HW;
+} mzba_sink;
+
+/* Reset: _pad_initial_state (train_torch.py:313-332): frame-history ring filled with g(s0), action ring filled with
+ * pad_action (0 for the acting loop, 1 for run_test_simulation, train_torch.py:545), hist_len = 0. Random draws as
+ * mzba_env_reset_planes. */
+int mzba_env_reset_compact(const mzba_env_state* env, uint64_t seed, int episode, int env_offset,
+                           const int32_t* params, int pad_action, hipStream_t stream);
 
 /* Streaming acting: launched at the head of acting step t = ctx[2], before the rep input is built.
  * Every env with done != 0 or hist_len >= blk[1] (the per-episode record cap) is reset in place exactly as
@@ -57,44 +85,35 @@ int mzba_env_reset_compact(int32_t* paddle, int32_t* bx, int32_t* by, int32_t* d
  * 0 = no episode of env b starts at row t, else bit 31 | paddle | bx << 10 | by << 20 of s0 (g(s0) can be rendered
  * from the word alone). At t == 0 nothing is reset and every env's word is written from its current state (the state
  * the stage's mzba_env_reset_compact left). H, W <= 256. */
-int mzba_env_restart_compact(int32_t* paddle, int32_t* bx, int32_t* by, int32_t* dx, float* dy, uint8_t* done,
-                             uint64_t* bricks, int nw, uint8_t* cur_frame, uint8_t* cur_src, uint8_t* hist_frames,
-                             uint8_t* hist_actions, int32_t* hist_len, int L, uint32_t* start, const int32_t* ctx,
-                             const int32_t* blk, int B, int H, int W, int paddle_width, int brick_rows, uint64_t seed,
-                             int env_offset, const int32_t* params, int pad_action, hipStream_t stream);
+int mzba_env_restart_compact(const mzba_env_state* env, uint32_t* start, const int32_t* ctx, const int32_t* blk,
+                             uint64_t seed, int env_offset, const int32_t* params, int pad_action,
+                             hipStream_t stream);
 
 /* One acting-loop env step (train_torch.py:201-209): step, render the u8 gray frame, push
  * (action, frame) into the history ring when the env is recorded (not prev_done; at the first
- * step prev_done aliases done, :179), and write the trajectory-sink row (rec_* may be NULL).
+ * step prev_done aliases done, :179), and write the trajectory-sink row: rec's action, reward, mask and frame
+ * (frame may be NULL; rec = NULL: no sink; rec->B, and rec->HW with a frame, must be the env's).
  * ctx (optional, graph replay): device int32[3] step context; when given, the sink row is
- * ctx[2] (rec_* are the (T,B,..) bases) and first_step = (ctx[2] == 0). */
+ * ctx[2] (rec's fields are the (T,B,..) bases) and first_step = (ctx[2] == 0); without it they are the row to write. */
 /* rec_flags: 0 = record envs that were live before the step (the acting loop); bit 0 = record every
  * env, bit 1 = record env 0's action for every env (run_test_simulation, train_torch.py:594-598). */
-int mzba_env_step_compact(int32_t* paddle, int32_t* bx, int32_t* by, int32_t* dx, float* dy, uint8_t* done,
-                          uint64_t* bricks, int nw, const int64_t* action, float* reward, float* valid,
-                          uint8_t* cur_frame, uint8_t* cur_src, uint8_t* hist_frames, uint8_t* hist_actions,
-                          int32_t* hist_len, int L, uint8_t* rec_action, float* rec_reward, uint8_t* rec_mask, uint8_t* rec_frame,
-                          int first_step, int B, int H, int W, int paddle_width, int brick_rows,
-                          const float* rewards4, const int32_t* ctx, int rec_flags, hipStream_t stream);
+int mzba_env_step_compact(const mzba_env_state* env, const int64_t* action, float* reward, float* valid,
+                          const mzba_sink* rec, int first_step, const float* rewards4, const int32_t* ctx,
+                          int rec_flags, hipStream_t stream);
 
 /* Diagnostics: envs per workgroup of mzba_env_step_compact (0 = automatic). */
 int mzba_env_set_block_envs(int E);
 
 /* compact -> reference planes (B,3,H,W) f32. */
-int mzba_compact_to_planes(const int32_t* paddle, const int32_t* bx, const int32_t* by, const uint8_t* done,
-                           const uint64_t* bricks, int nw, float* planes, int B, int H, int W, int paddle_width,
-                           int brick_rows, hipStream_t stream);
+int mzba_compact_to_planes(const mzba_env_state* env, float* planes, hipStream_t stream);
 
 /* RLSystem._prepare_mcts_input + _encode_actions (train_torch.py:259-293) for all envs:
  * NHWC out [B][HW][Cs] (f32 or bf16): L-1 ring frames oldest first, the current frame, L action
  * planes a/3, zero padding to Cs. */
-int mzba_build_rep_input(const uint8_t* cur_frame, const uint8_t* cur_src, const uint8_t* hist_frames,
-                         const uint8_t* hist_actions, const int32_t* hist_len, int L, void* out, int out_bf16, int B,
-                         int HW, int Cs, hipStream_t stream);
+int mzba_build_rep_input(const mzba_env_state* env, void* out, int out_bf16, int Cs, hipStream_t stream);
 
 /* Every env's current frame [B][HW] u8 gray codes (for host readers: frame logging, tests). */
-int mzba_env_current_frame(const uint8_t* cur_frame, const uint8_t* cur_src, const uint8_t* hist_frames,
-                           const int32_t* hist_len, int L, uint8_t* out, int B, int HW, hipStream_t stream);
+int mzba_env_current_frame(const mzba_env_state* env, uint8_t* out, hipStream_t stream);
 
 /* ---- networks (src/networks.py) -------------------------------------------------------- */
 
@@ -265,25 +284,30 @@ int mzba_conv_band_res(const void* in, const void* w1, const float* b1, const vo
                        int B, int H, int W, int C, hipStream_t stream);
 
 /* Replay ingest on the device (replay_buffer.py:96-165, train_torch.py:223-225). Records of one episode
- * batch as the acting loop's sink holds them: action u8 [T][B], reward f32 [T][B], mask u8 [T][B]
- * (recorded = not prev_done, a prefix), counts i64 [T][B][3], value f32 [T][B], frame u8 [T][B][HW]
- * gray codes, frame0 u8 [B][HW] = g(s0).
+ * batch as the acting loop's sink holds them (mzba_sink; mask = recorded = not prev_done, a prefix; T = the rows
+ * used), frame0 u8 [B][HW] = g(s0).
  * plan: lens i32[B], rsum f32[B] (reward sums), offsets i32[B+1] = exclusive scan of the window counts
- *       (L - K + 1 for trajectories with L > min_len, else 0).
- * write: windows [j0, n) with j0 = max(0, n - cap) into ring slots (head + j) % cap: past actions
- *       i64 [cap][hist], future actions i64 [cap][K], frames u8 [cap][hist][HW], rewards / values /
- *       n-step targets f32 [cap][K], counts f32 [cap][K][3], reward sum f32 [cap]; dpow f32[T + 2]:
- *       dpow[k] = f32(discount**k) for k <= T, dpow[T + 1] = f32(discount**K) (python double pow).
+ *       (L - K + 1 for trajectories with L > min_len, else 0). Reads the sink's mask and reward.
+ * write: windows [j0, n) with j0 = max(0, n - cap) into ring slots (head + j) % cap of the ring; dpow f32[T + 2]:
+ *       dpow[k] = f32(discount**k) for k <= T, dpow[T + 1] = f32(discount**K) (python double pow). Reads every
+ *       sink field but start.
  * states: out f32 [n][hist][HW] = lut8[code & 7] for ring slots slots[n] (the learner's input). */
-int mzba_replay_plan(const uint8_t* action, const float* reward, const uint8_t* mask, const int64_t* counts,
-                     const float* value, const uint8_t* frame, const uint8_t* frame0, int T, int B, int HW, int K,
-                     int min_len, int32_t* lens, float* rsum, int32_t* offsets, hipStream_t stream);
-int mzba_replay_write(const uint8_t* action, const float* reward, const uint8_t* mask, const int64_t* counts,
-                      const float* value, const uint8_t* frame, const uint8_t* frame0, int T, int B, int HW,
-                      const int32_t* lens, const float* rsum, const int32_t* offsets, int n_windows,
-                      int64_t* past_actions, int64_t* future_actions, uint8_t* states, float* rewards,
-                      float* counts_out, float* values_out, float* targets, float* reward_sum, int cap, int head,
-                      int K, int hist, const float* dpow, hipStream_t stream);
+typedef struct mzba_replay_ring {
+  int64_t* past_actions;    /* i64 [cap][hist] */
+  int64_t* future_actions;  /* i64 [cap][K] */
+  uint8_t* states;          /* u8 [cap][hist][HW] gray codes */
+  float* rewards;           /* f32 [cap][K] */
+  float* counts;            /* f32 [cap][K][3] */
+  float* values;            /* f32 [cap][K] */
+  float* targets;           /* f32 [cap][K] n-step targets */
+  float* reward_sum;        /* f32 [cap] */
+  int cap, K, hist;         /* rows; unroll steps; frames per window (hist >= 2, hist + K < 256) */
+} mzba_replay_ring;
+int mzba_replay_plan(const mzba_sink* sink, const uint8_t* frame0, int K, int min_len, int32_t* lens, float* rsum,
+                     int32_t* offsets, hipStream_t stream);
+int mzba_replay_write(const mzba_sink* sink, const uint8_t* frame0, const int32_t* lens, const float* rsum,
+                      const int32_t* offsets, int n_windows, const mzba_replay_ring* ring, int head,
+                      const float* dpow, hipStream_t stream);
 int mzba_replay_states(const uint8_t* states, const int32_t* slots, int n, const float* lut8, float* out, int hist,
                        int HW, hipStream_t stream);
 
@@ -296,17 +320,15 @@ int mzba_replay_states(const uint8_t* states, const int32_t* slots, int n, const
  *   [6][nmax + 1]: per kept segment env, start row, length, reward sum (f32 bits), start word, window offset
  *   (entry [segments] = windows). nmax >= B * (T / max(min_len + 1, K)) or -2.
  * stream_write: mzba_replay_write for the table's windows: records from the segment's start row on, the 31 pad frames
- *   g(s0) rendered from the start word (H, W <= 256, paddle_width, brick_rows as in the env). Same ring rows,
- *   arithmetic and eviction rule. */
-int mzba_replay_stream_plan(const float* reward, const uint8_t* mask, const uint32_t* start, const uint8_t* done,
-                            const int32_t* hlen, int T, int B, int K, int min_len, int cap_len, int keep_tail,
-                            int32_t* cnt, int32_t* offs, int32_t* table, int nmax, hipStream_t stream);
-int mzba_replay_stream_write(const uint8_t* action, const float* reward, const int64_t* counts, const float* value,
-                             const uint8_t* frame, int T, int B, int H, int W, int paddle_width, int brick_rows,
-                             const int32_t* table, int nmax, int n_segments, int n_windows, int64_t* past_actions,
-                             int64_t* future_actions, uint8_t* states, float* rewards, float* counts_out,
-                             float* values_out, float* targets, float* reward_sum, int cap, int head, int K, int hist,
-                             const float* dpow, hipStream_t stream);
+ *   g(s0) rendered from the start word (H, W <= 256, paddle_width, brick_rows as in the env; sink->HW == H * W).
+ *   Same ring rows, arithmetic and eviction rule. stream_plan reads the sink's reward, mask and start; stream_write
+ *   its action, reward, counts, values and frame. */
+int mzba_replay_stream_plan(const mzba_sink* sink, const uint8_t* done, const int32_t* hlen, int K, int min_len,
+                            int cap_len, int keep_tail, int32_t* cnt, int32_t* offs, int32_t* table, int nmax,
+                            hipStream_t stream);
+int mzba_replay_stream_write(const mzba_sink* sink, int H, int W, int paddle_width, int brick_rows,
+                             const int32_t* table, int nmax, int n_segments, int n_windows,
+                             const mzba_replay_ring* ring, int head, const float* dpow, hipStream_t stream);
 
 /* ===================== prioritized replay (MuZero, Appendix G; csrc/replay_prio.hip)
  * q f32[cap], 16-byte aligned, in slot space: q[slot] = p^alpha for a live window, exactly 0 for a slot that
@@ -536,10 +558,10 @@ int mzba_sample_actions(const int64_t* counts, int64_t* action, float* probs_out
 int mzba_torch_pow(const int64_t* counts, float* out, long long n, double e, long long start, long long n_total,
                    int vec_block, int pow_threads, hipStream_t stream);
 
-/* Trajectory-sink row of the search results: rec_counts[t][b] = counts[b], rec_values[t][b] = values[b],
- * t = ctx ? ctx[2] : t (replay_buffer.py:17-35 visit_counts / values). */
-int mzba_record_results(const int64_t* counts, const float* values, int64_t* rec_counts, float* rec_values, int B,
-                        int t, const int32_t* ctx, hipStream_t stream);
+/* Trajectory-sink row of the search results: rec->counts[t][b] = counts[b], rec->values[t][b] = values[b] for the
+ * rec->B envs, t = ctx ? ctx[2] : t (replay_buffer.py:17-35 visit_counts / values). */
+int mzba_record_results(const int64_t* counts, const float* values, const mzba_sink* rec, int t, const int32_t* ctx,
+                        hipStream_t stream);
 
 /* ctx[0..2] += 1 (end of one captured acting step). */
 int mzba_ctx_advance(int32_t* ctx, hipStream_t stream);
@@ -744,6 +766,10 @@ int mzba_guard_restore(const void* table, int ntensors, const mzba_guard_block* 
 /* mzba_replay_priority_update that leaves q untouched when block->skip != 0 (csrc/replay_prio.hip). */
 int mzba_replay_priority_update_g(float* q, const int32_t* slots, const float* td, int n, int cap, float alpha,
                                   float eps, const mzba_guard_block* block, hipStream_t stream);
+
+/* sizeof of an ABI struct by its name (mzba_env_state, mzba_sink, mzba_replay_ring, mzba_tower_ext,
+ * mzba_tree_step), -1 for another name: a binding checks its mirror of each struct against it when it loads. */
+int mzba_struct_bytes(const char* name);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,8 @@
 //    fused acting loop. Phase 1 = one thread per env (branchy scalar rules), phase 2 =
 //    the workgroup renders its envs' uint8 gray-code frames with 16-B coalesced stores
 //    and pushes them into the frame-history ring (train_torch.py:201-209, 259-293).
+#include <string.h>
+
 #include "common.h"
 
 namespace {
@@ -519,6 +521,13 @@ __global__ void current_frame_kernel(const uint8_t* __restrict__ cur_frame, Hist
   for (int p = threadIdx.x; p < HW; p += blockDim.x) out[(size_t)b * HW + p] = src[p];
 }
 
+// the kernels' views of the ABI's env state (include/mzba.h)
+struct EnvViews { Compact cs; History h; };
+EnvViews views(const mzba_env_state& e) {
+  return {{e.paddle, e.bx, e.by, e.dx, e.dy, e.done, e.bricks, e.nw},
+          {e.hist_frames, e.hist_actions, e.hist_len, e.L, e.cur_src}};
+}
+
 }  // namespace
 
 static thread_local int g_block_envs = 0;  // 0 = automatic (mzba_env_set_block_envs, diagnostics)
@@ -562,100 +571,102 @@ int mzba_grayscale_planes(const float* state, float* gray, int B, int H, int W, 
   return 0;
 }
 
-int mzba_env_reset_compact(int32_t* paddle, int32_t* bx, int32_t* by, int32_t* dx, float* dy, uint8_t* done,
-                           uint64_t* bricks, int nw, uint8_t* cur_frame, uint8_t* cur_src, uint8_t* hist_frames,
-                           uint8_t* hist_actions, int32_t* hist_len, int L, int B, int H, int W, int paddle_width,
-                           int brick_rows, uint64_t seed, int episode, int env_offset, const int32_t* params,
-                           int pad_action, hipStream_t stream) {
-  MZ_CHECK_ARG(B > 0 && L >= 2 && nw * 64 >= brick_rows * W && nw <= 4 && (H * W) % 16 == 0 && pad_action >= 0 &&
-               pad_action < 3, -1);
-  Compact cs{paddle, bx, by, dx, dy, done, bricks, nw};
-  History h{hist_frames, hist_actions, hist_len, L, cur_src};
-  hipLaunchKernelGGL(env_reset_compact_kernel, dim3(B), dim3(256), 0, stream, cs, cur_frame, h, pad_action, B, H, W,
-                     paddle_width, brick_rows, seed, episode, env_offset, params);
+int mzba_env_reset_compact(const mzba_env_state* env, uint64_t seed, int episode, int env_offset,
+                           const int32_t* params, int pad_action, hipStream_t stream) {
+  MZ_CHECK_ARG(env, -1);
+  const mzba_env_state& e = *env;
+  MZ_CHECK_ARG(e.B > 0 && e.L >= 2 && e.nw * 64 >= e.brick_rows * e.W && e.nw <= 4 && (e.H * e.W) % 16 == 0 &&
+               pad_action >= 0 && pad_action < 3, -1);
+  const EnvViews v = views(e);
+  hipLaunchKernelGGL(env_reset_compact_kernel, dim3(e.B), dim3(256), 0, stream, v.cs, e.cur_frame, v.h, pad_action,
+                     e.B, e.H, e.W, e.paddle_width, e.brick_rows, seed, episode, env_offset, params);
   MZ_LAUNCH_CHECK();
   return 0;
 }
 
-int mzba_env_restart_compact(int32_t* paddle, int32_t* bx, int32_t* by, int32_t* dx, float* dy, uint8_t* done,
-                             uint64_t* bricks, int nw, uint8_t* cur_frame, uint8_t* cur_src, uint8_t* hist_frames,
-                             uint8_t* hist_actions, int32_t* hist_len, int L, uint32_t* start, const int32_t* ctx,
-                             const int32_t* blk, int B, int H, int W, int paddle_width, int brick_rows, uint64_t seed,
-                             int env_offset, const int32_t* params, int pad_action, hipStream_t stream) {
-  MZ_CHECK_ARG(B > 0 && L >= 2 && nw >= 1 && nw * 64 >= brick_rows * W && nw <= 4 && (H * W) % 16 == 0 && H <= 256 &&
-               W <= 256 && pad_action >= 0 && pad_action < 3 && start && ctx && blk, -1);
-  Compact cs{paddle, bx, by, dx, dy, done, bricks, nw};
-  History h{hist_frames, hist_actions, hist_len, L, cur_src};
-  hipLaunchKernelGGL(env_restart_compact_kernel, dim3((B + RE - 1) / RE), dim3(256), 0, stream, cs, cur_frame, h, start,
-                     ctx, blk, pad_action, B, H, W, paddle_width, brick_rows, seed, env_offset, params);
+int mzba_env_restart_compact(const mzba_env_state* env, uint32_t* start, const int32_t* ctx, const int32_t* blk,
+                             uint64_t seed, int env_offset, const int32_t* params, int pad_action,
+                             hipStream_t stream) {
+  MZ_CHECK_ARG(env, -1);
+  const mzba_env_state& e = *env;
+  MZ_CHECK_ARG(e.B > 0 && e.L >= 2 && e.nw >= 1 && e.nw * 64 >= e.brick_rows * e.W && e.nw <= 4 &&
+               (e.H * e.W) % 16 == 0 && e.H <= 256 && e.W <= 256 && pad_action >= 0 && pad_action < 3 && start &&
+               ctx && blk, -1);
+  const EnvViews v = views(e);
+  hipLaunchKernelGGL(env_restart_compact_kernel, dim3((e.B + RE - 1) / RE), dim3(256), 0, stream, v.cs, e.cur_frame,
+                     v.h, start, ctx, blk, pad_action, e.B, e.H, e.W, e.paddle_width, e.brick_rows, seed, env_offset,
+                     params);
   MZ_LAUNCH_CHECK();
   return 0;
 }
 
-int mzba_env_step_compact(int32_t* paddle, int32_t* bx, int32_t* by, int32_t* dx, float* dy, uint8_t* done,
-                          uint64_t* bricks, int nw, const int64_t* action, float* reward, float* valid,
-                          uint8_t* cur_frame, uint8_t* cur_src, uint8_t* hist_frames, uint8_t* hist_actions,
-                          int32_t* hist_len, int L, uint8_t* rec_action, float* rec_reward, uint8_t* rec_mask, uint8_t* rec_frame,
-                          int first_step, int B, int H, int W, int paddle_width, int brick_rows,
-                          const float* rewards4, const int32_t* ctx, int rec_flags, hipStream_t stream) {
-  MZ_CHECK_ARG(B > 0 && L >= 2 && nw >= 1 && nw <= 4 && nw * 64 >= brick_rows * W && (H * W) % 16 == 0 &&
-               H * W <= 65536 && rewards4, -1);  // H*W bound: the render loop's reciprocal division
-  Compact cs{paddle, bx, by, dx, dy, done, bricks, nw};
-  History h{hist_frames, hist_actions, hist_len, L, cur_src};
-  Sink sk{rec_action, rec_reward, rec_mask, rec_frame};
+int mzba_env_step_compact(const mzba_env_state* env, const int64_t* action, float* reward, float* valid,
+                          const mzba_sink* rec, int first_step, const float* rewards4, const int32_t* ctx,
+                          int rec_flags, hipStream_t stream) {
+  MZ_CHECK_ARG(env, -1);
+  const mzba_env_state& e = *env;
+  MZ_CHECK_ARG(e.B > 0 && e.L >= 2 && e.nw >= 1 && e.nw <= 4 && e.nw * 64 >= e.brick_rows * e.W &&
+               (e.H * e.W) % 16 == 0 && e.H * e.W <= 65536 && rewards4, -1);  // H*W bound: the render loop's reciprocal division
+  MZ_CHECK_ARG(!rec || (rec->B == e.B && (!rec->frame || rec->HW == e.H * e.W)), -1);  // rows are indexed with the env's sizes
+  const EnvViews v = views(e);
+  const Sink sk = rec ? Sink{rec->action, rec->reward, rec->mask, rec->frame} : Sink{};
   RewardCfg rc{rewards4[0], rewards4[1], rewards4[2], rewards4[3]};
   // envs per block: ~<= 4 16-B render stores per lane, and >= ~512 blocks when B allows
-  const int chunks = H * W / 16;
+  const int chunks = e.H * e.W / 16;
   int E = 1;
-  while (E < 256 && 2 * E * chunks <= 1024 && 2 * E * 512 <= B) E *= 2;
+  while (E < 256 && 2 * E * chunks <= 1024 && 2 * E * 512 <= e.B) E *= 2;
   if (g_block_envs > 0) E = g_block_envs;
-  dim3 grid((B + E - 1) / E);
-  if (nw == 1)
-    hipLaunchKernelGGL(env_step_compact_kernel<1>, grid, dim3(256), 0, stream, cs, action, reward, valid, cur_frame,
-                       h, sk, first_step, B, H, W, paddle_width, brick_rows, rc, ctx, E, rec_flags);
-  else
-    hipLaunchKernelGGL(env_step_compact_kernel<4>, grid, dim3(256), 0, stream, cs, action, reward, valid, cur_frame,
-                       h, sk, first_step, B, H, W, paddle_width, brick_rows, rc, ctx, E, rec_flags);
+  dim3 grid((e.B + E - 1) / E);
+  const auto kernel = e.nw == 1 ? env_step_compact_kernel<1> : env_step_compact_kernel<4>;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, v.cs, action, reward, valid, e.cur_frame, v.h, sk, first_step,
+                     e.B, e.H, e.W, e.paddle_width, e.brick_rows, rc, ctx, E, rec_flags);
   MZ_LAUNCH_CHECK();
   return 0;
 }
 
-int mzba_compact_to_planes(const int32_t* paddle, const int32_t* bx, const int32_t* by, const uint8_t* done,
-                           const uint64_t* bricks, int nw, float* planes, int B, int H, int W, int paddle_width,
-                           int brick_rows, hipStream_t stream) {
-  MZ_CHECK_ARG(B > 0, -1);
-  Compact cs{(int32_t*)paddle, (int32_t*)bx, (int32_t*)by, nullptr, nullptr, (uint8_t*)done, (uint64_t*)bricks, nw};
-  hipLaunchKernelGGL(compact_to_planes_kernel, dim3(B), dim3(256), 0, stream, cs, planes, H, W, paddle_width,
-                     brick_rows);
+int mzba_compact_to_planes(const mzba_env_state* env, float* planes, hipStream_t stream) {
+  MZ_CHECK_ARG(env && env->B > 0, -1);
+  hipLaunchKernelGGL(compact_to_planes_kernel, dim3(env->B), dim3(256), 0, stream, views(*env).cs, planes, env->H,
+                     env->W, env->paddle_width, env->brick_rows);
   MZ_LAUNCH_CHECK();
   return 0;
 }
 
-int mzba_build_rep_input(const uint8_t* cur_frame, const uint8_t* cur_src, const uint8_t* hist_frames,
-                         const uint8_t* hist_actions, const int32_t* hist_len, int L, void* out, int out_bf16, int B,
-                         int HW, int Cs, hipStream_t stream) {
-  MZ_CHECK_ARG(B > 0 && Cs >= 2 * L && Cs % 8 == 0, -1);
-  History h{(uint8_t*)hist_frames, (uint8_t*)hist_actions, (int32_t*)hist_len, L, (uint8_t*)cur_src};
+int mzba_build_rep_input(const mzba_env_state* env, void* out, int out_bf16, int Cs, hipStream_t stream) {
+  MZ_CHECK_ARG(env && env->B > 0 && Cs >= 2 * env->L && Cs % 8 == 0, -1);
+  const History h = views(*env).h;
+  const int B = env->B, HW = env->H * env->W;
   size_t n = (size_t)B * HW * (Cs / 8);
   unsigned grid = (unsigned)((n + 255) / 256);
   if (grid > 16384) grid = 16384;
   if (out_bf16)
-    hipLaunchKernelGGL(build_rep_input_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, cur_frame, h,
+    hipLaunchKernelGGL(build_rep_input_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, env->cur_frame, h,
                        (bf16_t*)out, B, HW, Cs);
   else
-    hipLaunchKernelGGL(build_rep_input_kernel<float>, dim3(grid), dim3(256), 0, stream, cur_frame, h, (float*)out,
+    hipLaunchKernelGGL(build_rep_input_kernel<float>, dim3(grid), dim3(256), 0, stream, env->cur_frame, h, (float*)out,
                        B, HW, Cs);
   MZ_LAUNCH_CHECK();
   return 0;
 }
 
-int mzba_env_current_frame(const uint8_t* cur_frame, const uint8_t* cur_src, const uint8_t* hist_frames,
-                           const int32_t* hist_len, int L, uint8_t* out, int B, int HW, hipStream_t stream) {
-  MZ_CHECK_ARG(B > 0 && L >= 2 && HW > 0 && out, -1);
-  History h{(uint8_t*)hist_frames, nullptr, (int32_t*)hist_len, L, (uint8_t*)cur_src};
-  hipLaunchKernelGGL(current_frame_kernel, dim3(B), dim3(256), 0, stream, cur_frame, h, out, B, HW);
+int mzba_env_current_frame(const mzba_env_state* env, uint8_t* out, hipStream_t stream) {
+  MZ_CHECK_ARG(env && env->B > 0 && env->L >= 2 && env->H * env->W > 0 && out, -1);
+  hipLaunchKernelGGL(current_frame_kernel, dim3(env->B), dim3(256), 0, stream, env->cur_frame, views(*env).h, out,
+                     env->B, env->H * env->W);
   MZ_LAUNCH_CHECK();
   return 0;
+}
+
+int mzba_struct_bytes(const char* name) {
+  MZ_CHECK_ARG(name, -1);
+#define MZ_STRUCT_BYTES(T) if (!strcmp(name, #T)) return (int)sizeof(T)
+  MZ_STRUCT_BYTES(mzba_env_state);
+  MZ_STRUCT_BYTES(mzba_sink);
+  MZ_STRUCT_BYTES(mzba_replay_ring);
+  MZ_STRUCT_BYTES(mzba_tower_ext);
+  MZ_STRUCT_BYTES(mzba_tree_step);
+#undef MZ_STRUCT_BYTES
+  return -1;
 }
 
 }  // extern "C"

@@ -251,11 +251,11 @@ int mzba_torch_pow(const int64_t* counts, float* out, long long n, double e, lon
   return 0;
 }
 
-int mzba_record_results(const int64_t* counts, const float* values, int64_t* rec_counts, float* rec_values, int B,
-                        int t, const int32_t* ctx, hipStream_t stream) {
-  MZ_CHECK_ARG(B > 0, -1);
-  hipLaunchKernelGGL(record_results_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, counts, values, rec_counts,
-                     rec_values, B, t, ctx);
+int mzba_record_results(const int64_t* counts, const float* values, const mzba_sink* rec, int t, const int32_t* ctx,
+                        hipStream_t stream) {
+  MZ_CHECK_ARG(rec && rec->B > 0, -1);
+  hipLaunchKernelGGL(record_results_kernel, dim3((rec->B + 255) / 256), dim3(256), 0, stream, counts, values,
+                     rec->counts, rec->values, rec->B, t, ctx);
   MZ_LAUNCH_CHECK();
   return 0;
 }

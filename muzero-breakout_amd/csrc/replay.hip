@@ -274,49 +274,60 @@ __global__ __launch_bounds__(256) void replay_states_kernel(const uint8_t* __res
   }
 }
 
+// the kernels' views of the ABI's sink and ring (include/mzba.h)
+ReplayRecords records(const mzba_sink& s, const uint8_t* frame0) {
+  return {s.action, s.reward, s.mask, s.counts, s.values, s.frame, frame0, s.T, s.B, s.HW};
+}
+ReplayRing ring_view(const mzba_replay_ring& g) {
+  return {g.past_actions, g.future_actions, g.states, g.rewards, g.counts, g.values, g.targets, g.reward_sum, g.cap};
+}
+
+// what both writers ask of the ring and of the window range
+bool ring_ok(const mzba_replay_ring* g, int head, int n_windows) {
+  return g && g->K > 0 && g->hist >= 2 && g->hist + g->K < 256 && g->cap > 0 && head >= 0 && head < g->cap &&
+         n_windows >= 0 && g->past_actions && g->future_actions && g->states && g->rewards && g->counts && g->values &&
+         g->targets && g->reward_sum;
+}
+
 }  // namespace
 
 extern "C" {
 
-int mzba_replay_plan(const uint8_t* action, const float* reward, const uint8_t* mask, const int64_t* counts,
-                     const float* value, const uint8_t* frame, const uint8_t* frame0, int T, int B, int HW, int K,
-                     int min_len, int32_t* lens, float* rsum, int32_t* offsets, hipStream_t stream) {
-  MZ_CHECK_ARG(T > 0 && B > 0 && HW > 0 && K > 0 && mask && reward && lens && rsum && offsets, -1);
-  ReplayRecords r{action, reward, mask, counts, value, frame, frame0, T, B, HW};
-  hipLaunchKernelGGL(replay_plan_kernel, dim3(1), dim3(PT), 0, stream, r, K, min_len, lens, rsum, offsets);
+int mzba_replay_plan(const mzba_sink* sink, const uint8_t* frame0, int K, int min_len, int32_t* lens, float* rsum,
+                     int32_t* offsets, hipStream_t stream) {
+  MZ_CHECK_ARG(sink && sink->T > 0 && sink->B > 0 && sink->HW > 0 && K > 0 && sink->mask && sink->reward && lens &&
+               rsum && offsets, -1);
+  hipLaunchKernelGGL(replay_plan_kernel, dim3(1), dim3(PT), 0, stream, records(*sink, frame0), K, min_len, lens,
+                     rsum, offsets);
   MZ_LAUNCH_CHECK();
   return 0;
 }
 
-int mzba_replay_write(const uint8_t* action, const float* reward, const uint8_t* mask, const int64_t* counts,
-                      const float* value, const uint8_t* frame, const uint8_t* frame0, int T, int B, int HW,
-                      const int32_t* lens, const float* rsum, const int32_t* offsets, int n_windows,
-                      int64_t* past_actions, int64_t* future_actions, uint8_t* states, float* rewards,
-                      float* counts_out, float* values_out, float* targets, float* reward_sum, int cap, int head,
-                      int K, int hist, const float* dpow, hipStream_t stream) {
-  MZ_CHECK_ARG(T > 0 && B > 0 && HW % 16 == 0 && K > 0 && hist >= 2 && hist + K < 256 && cap > 0 &&
-               head >= 0 && head < cap && n_windows >= 0, -1);
-  MZ_CHECK_ARG(dpow && action && reward && counts && value && frame && frame0 && lens && rsum && offsets && past_actions &&
-               future_actions && states && rewards && counts_out && values_out && targets && reward_sum, -1);
+int mzba_replay_write(const mzba_sink* sink, const uint8_t* frame0, const int32_t* lens, const float* rsum,
+                      const int32_t* offsets, int n_windows, const mzba_replay_ring* ring, int head,
+                      const float* dpow, hipStream_t stream) {
+  MZ_CHECK_ARG(sink && sink->T > 0 && sink->B > 0 && sink->HW % 16 == 0 && ring_ok(ring, head, n_windows), -1);
+  MZ_CHECK_ARG(dpow && sink->action && sink->reward && sink->counts && sink->values && sink->frame && frame0 && lens &&
+               rsum && offsets, -1);
   if (n_windows == 0) return 0;
-  ReplayRecords r{action, reward, mask, counts, value, frame, frame0, T, B, HW};
-  ReplayRing g{past_actions, future_actions, states, rewards, counts_out, values_out, targets, reward_sum, cap};
-  const int j0 = n_windows > cap ? n_windows - cap : 0;  // older windows would be evicted at once
-  hipLaunchKernelGGL(replay_write_kernel, dim3(n_windows - j0), dim3(256), 0, stream, r, g, lens, rsum, offsets, K,
-                     hist, dpow, head, j0);
+  const int j0 = n_windows > ring->cap ? n_windows - ring->cap : 0;  // older windows would be evicted at once
+  hipLaunchKernelGGL(replay_write_kernel, dim3(n_windows - j0), dim3(256), 0, stream, records(*sink, frame0),
+                     ring_view(*ring), lens, rsum, offsets, ring->K, ring->hist, dpow, head, j0);
   MZ_LAUNCH_CHECK();
   return 0;
 }
 
-int mzba_replay_stream_plan(const float* reward, const uint8_t* mask, const uint32_t* start, const uint8_t* done,
-                            const int32_t* hlen, int T, int B, int K, int min_len, int cap_len, int keep_tail,
-                            int32_t* cnt, int32_t* offs, int32_t* table, int nmax, hipStream_t stream) {
-  MZ_CHECK_ARG(T > 0 && B > 0 && K > 0 && reward && mask && start && done && hlen && cnt && offs && table, -1);
+int mzba_replay_stream_plan(const mzba_sink* sink, const uint8_t* done, const int32_t* hlen, int K, int min_len,
+                            int cap_len, int keep_tail, int32_t* cnt, int32_t* offs, int32_t* table, int nmax,
+                            hipStream_t stream) {
+  MZ_CHECK_ARG(sink && sink->T > 0 && sink->B > 0 && K > 0 && sink->reward && sink->mask && sink->start && done &&
+               hlen && cnt && offs && table, -1);
+  const int B = sink->B;
   // a kept segment holds at least max(min_len + 1, K) of its env's T rows
   const int keep = (min_len + 1 > K ? min_len + 1 : K);
-  MZ_CHECK_ARG(nmax >= 0 && (long long)nmax >= (long long)B * (T / keep), -2);
-  ReplayRecords r{nullptr, reward, mask, nullptr, nullptr, nullptr, nullptr, T, B, 0};
-  StreamPlan p{start, done, hlen, cap_len, keep_tail, K, min_len};
+  MZ_CHECK_ARG(nmax >= 0 && (long long)nmax >= (long long)B * (sink->T / keep), -2);
+  const ReplayRecords r = records(*sink, nullptr);
+  StreamPlan p{sink->start, done, hlen, cap_len, keep_tail, K, min_len};
   SegTable tb{table, nmax};
   const dim3 grid((B + 255) / 256);
   hipLaunchKernelGGL(stream_count_kernel, grid, dim3(256), 0, stream, r, p, cnt);
@@ -326,25 +337,20 @@ int mzba_replay_stream_plan(const float* reward, const uint8_t* mask, const uint
   return 0;
 }
 
-int mzba_replay_stream_write(const uint8_t* action, const float* reward, const int64_t* counts, const float* value,
-                             const uint8_t* frame, int T, int B, int H, int W, int paddle_width, int brick_rows,
-                             const int32_t* table, int nmax, int n_segments, int n_windows, int64_t* past_actions,
-                             int64_t* future_actions, uint8_t* states, float* rewards, float* counts_out,
-                             float* values_out, float* targets, float* reward_sum, int cap, int head, int K, int hist,
-                             const float* dpow, hipStream_t stream) {
-  MZ_CHECK_ARG(T > 0 && B > 0 && H > 0 && W > 0 && H <= 256 && W <= 256 && (H * W) % 16 == 0 && K > 0 && hist >= 2 &&
-               hist + K < 256 && cap > 0 && head >= 0 && head < cap && n_windows >= 0 && n_segments >= 0 &&
-               n_segments <= nmax && n_segments <= n_windows, -1);
-  MZ_CHECK_ARG(dpow && action && reward && counts && value && frame && table && past_actions && future_actions &&
-               states && rewards && counts_out && values_out && targets && reward_sum, -1);
+int mzba_replay_stream_write(const mzba_sink* sink, int H, int W, int paddle_width, int brick_rows,
+                             const int32_t* table, int nmax, int n_segments, int n_windows,
+                             const mzba_replay_ring* ring, int head, const float* dpow, hipStream_t stream) {
+  MZ_CHECK_ARG(sink && sink->T > 0 && sink->B > 0 && H > 0 && W > 0 && H <= 256 && W <= 256 && (H * W) % 16 == 0 &&
+               sink->HW == H * W && ring_ok(ring, head, n_windows) && n_segments >= 0 && n_segments <= nmax &&
+               n_segments <= n_windows, -1);
+  MZ_CHECK_ARG(dpow && sink->action && sink->reward && sink->counts && sink->values && sink->frame && table, -1);
   if (n_windows == 0) return 0;
   MZ_CHECK_ARG(n_segments > 0, -1);
-  ReplayRecords r{action, reward, nullptr, counts, value, frame, nullptr, T, B, H * W};
-  ReplayRing g{past_actions, future_actions, states, rewards, counts_out, values_out, targets, reward_sum, cap};
   SegTable tb{const_cast<int32_t*>(table), nmax};
-  const int j0 = n_windows > cap ? n_windows - cap : 0;  // older windows would be evicted at once
-  hipLaunchKernelGGL(stream_write_kernel, dim3(n_windows - j0), dim3(256), 0, stream, r, g, tb, n_segments, H, W,
-                     paddle_width, brick_rows, K, hist, dpow, head, j0);
+  const int j0 = n_windows > ring->cap ? n_windows - ring->cap : 0;  // older windows would be evicted at once
+  hipLaunchKernelGGL(stream_write_kernel, dim3(n_windows - j0), dim3(256), 0, stream, records(*sink, nullptr),
+                     ring_view(*ring), tb, n_segments, H, W, paddle_width, brick_rows, ring->K, ring->hist, dpow, head,
+                     j0);
   MZ_LAUNCH_CHECK();
   return 0;
 }

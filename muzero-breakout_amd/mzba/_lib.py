@@ -26,11 +26,12 @@ SIGNATURES = {
     "mzba_env_reset_planes": [P, P, P, I, I, I, I, I, U64, I, I, P, P],
     "mzba_env_step_planes": [P, P, P, P, P, P, P, P, I, I, I, I, P, P, P],
     "mzba_grayscale_planes": [P, P, I, I, I, P],
-    "mzba_env_reset_compact": [P, P, P, P, P, P, P, I, P, P, P, P, P, I, I, I, I, I, I, U64, I, I, P, I, P],
-    "mzba_env_step_compact": [P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, I, P, P, P, P, I, I, I, I, I, I, P, P, I, P],
-    "mzba_compact_to_planes": [P, P, P, P, P, I, P, I, I, I, I, I, P],
-    "mzba_build_rep_input": [P, P, P, P, P, I, P, I, I, I, I, P],
-    "mzba_env_current_frame": [P, P, P, P, I, P, I, I, P],
+    # env / sink / ring arguments are the structs below (EnvState, Sink, ReplayRing), passed by reference
+    "mzba_env_reset_compact": [P, U64, I, I, P, I, P],
+    "mzba_env_step_compact": [P, P, P, P, P, I, P, P, I, P],
+    "mzba_compact_to_planes": [P, P, P],
+    "mzba_build_rep_input": [P, P, I, I, P],
+    "mzba_env_current_frame": [P, P, P],
     "mzba_env_set_block_envs": [I],
     "mzba_conv2d": [I, P, LL, P, LL, P, P, P, P, I, P, P, I, I, I, I, I, I, I, P],
     "mzba_conv2d_set_variant": [I],
@@ -62,13 +63,13 @@ SIGNATURES = {
     "mzba_rep_trunk": [P, P, P, P, I, I, I, P],
     "mzba_conv_band_supported": [I, I, I, I, I],
     "mzba_conv_band_set_xt": [I],
-    "mzba_replay_plan": [P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P],
-    "mzba_replay_write": [P, P, P, P, P, P, P, I, I, I, P, P, P, I, P, P, P, P, P, P, P, P, I, I, I, I, P, P],
+    "mzba_replay_plan": [P, P, I, I, P, P, P, P],
+    "mzba_replay_write": [P, P, P, P, P, I, P, I, P, P],
     "mzba_replay_states": [P, P, I, P, P, I, I, P],
     # streaming acting (env.hip restart, replay.hip segmented ingest)
-    "mzba_env_restart_compact": [P, P, P, P, P, P, P, I, P, P, P, P, P, I, P, P, P, I, I, I, I, I, U64, I, P, I, P],
-    "mzba_replay_stream_plan": [P, P, P, P, P, I, I, I, I, I, I, P, P, P, I, P],
-    "mzba_replay_stream_write": [P, P, P, P, P, I, I, I, I, I, I, P, I, I, I, P, P, P, P, P, P, P, P, I, I, I, I, P, P],
+    "mzba_env_restart_compact": [P, P, P, P, U64, I, P, I, P],
+    "mzba_replay_stream_plan": [P, P, P, I, I, I, I, P, P, P, I, P],
+    "mzba_replay_stream_write": [P, I, I, I, I, P, I, I, I, P, I, P, P],
     # prioritized replay (replay_prio.hip)
     "mzba_replay_priority_init": [P, P, P, I, I, I, I, F, F, P],
     "mzba_replay_priority_update": [P, P, P, I, I, F, F, P],
@@ -91,7 +92,7 @@ SIGNATURES = {
     "mzba_mcts_results": [P, P, P, P, P, P, P, P, P, I, I, I, I, U64, P, P, P, P],
     "mzba_sample_actions": [P, P, P, I, D, P, I, I, I, I, I, U64, P, P],
     "mzba_torch_pow": [P, P, LL, D, LL, LL, I, I, P],
-    "mzba_record_results": [P, P, P, P, I, I, P, P],
+    "mzba_record_results": [P, P, P, I, P, P],
     "mzba_ctx_advance": [P, P],
     # learner (learn.hip; mzba_conv_wpack / mzba_conv_pack_bf16* in pack.hip, mzba_conv_wgrad* in wgrad.hip)
     "mzba_bn_stats": [I, P, I, I, F, F, P, P, P, P, P, P, LL, P],
@@ -145,6 +146,7 @@ SIGNATURES = {
     "mzba_guard_snapshot": [P, I, P],
     "mzba_guard_restore": [P, I, P, P],
     "mzba_replay_priority_update_g": [P, P, P, I, I, F, F, P, P],
+    "mzba_struct_bytes": [P],
 }
 
 _lib = None
@@ -168,6 +170,29 @@ class TowerExt(ctypes.Structure):
                 ("smin", F), ("smax", F), ("tree", ctypes.POINTER(TreeStep)), ("elem", I), ("plan", I)]
 
 
+class EnvState(ctypes.Structure):
+    """include/mzba.h mzba_env_state (the compact env and its history ring)."""
+    _fields_ = [("paddle", P), ("bx", P), ("by", P), ("dx", P), ("dy", P), ("done", P), ("bricks", P), ("nw", I),
+                ("cur_frame", P), ("cur_src", P), ("hist_frames", P), ("hist_actions", P), ("hist_len", P), ("L", I),
+                ("B", I), ("H", I), ("W", I), ("paddle_width", I), ("brick_rows", I)]
+
+
+class Sink(ctypes.Structure):
+    """include/mzba.h mzba_sink (the acting loop's trajectory sink)."""
+    _fields_ = [("action", P), ("reward", P), ("mask", P), ("counts", P), ("values", P), ("frame", P), ("start", P),
+                ("T", I), ("B", I), ("HW", I)]
+
+
+class ReplayRing(ctypes.Structure):
+    """include/mzba.h mzba_replay_ring (the replay buffer's rows)."""
+    _fields_ = [("past_actions", P), ("future_actions", P), ("states", P), ("rewards", P), ("counts", P),
+                ("values", P), ("targets", P), ("reward_sum", P), ("cap", I), ("K", I), ("hist", I)]
+
+
+# every struct of the ABI and its mirror here; lib() checks the sizes against mzba_struct_bytes
+STRUCTS = {"mzba_env_state": EnvState, "mzba_sink": Sink, "mzba_replay_ring": ReplayRing, "mzba_tower_ext": TowerExt,
+           "mzba_tree_step": TreeStep}
+
 # entry points that return something other than a status code
 RESTYPES = {"mzba_tower_ws_bytes": LL, "mzba_tower_plan": I, "mzba_conv_lat_get_variant": I, "mzba_conv_wgrad_ws_bytes": LL,
             "mzba_linear_ws_bytes": LL, "mzba_learner_loss_ws_bytes": LL, "mzba_replay_sample_ws_bytes": LL,
@@ -189,6 +214,10 @@ def lib():
             fn = getattr(L, name)
             fn.argtypes = argt
             fn.restype = RESTYPES.get(name, ctypes.c_int)
+        for name, cls in STRUCTS.items():
+            if L.mzba_struct_bytes(name.encode()) != ctypes.sizeof(cls):
+                raise RuntimeError(f"mzba: {LIB_PATH} was built with another {name} than this binding's "
+                                   f"({L.mzba_struct_bytes(name.encode())} bytes, {ctypes.sizeof(cls)} here)")
         _lib = L
     return _lib
 
@@ -234,6 +263,19 @@ def ptr(t):
     if t is None:
         return None
     return ctypes.c_void_p(t.data_ptr())
+
+
+def addr(t):
+    """A tensor's device address as a struct field's value (None: NULL)."""
+    return None if t is None else t.data_ptr()
+
+
+def sink(rec, T, HW, t=None):
+    """The `rec` dict of (T_max, B, ...) device tensors (missing or None entries: NULL) as a Sink of its first T
+    rows; with a row t, of that row alone (mzba_env_step_compact without a device step context)."""
+    g = rec.get if t is None else lambda k: None if rec.get(k) is None else rec[k][t]
+    return Sink(*(addr(g(k)) for k in ("action", "reward", "mask", "counts", "values", "frame", "start")),
+                T if t is None else 1, rec["action"].shape[1], HW)
 
 
 def call(name, *args):

@@ -8,6 +8,8 @@ sampling (:191-198) -> env step + gray render + history push + trajectory record
 trajectory sink (replay_buffer.py:ObservationTrajectory fields) that is copied to the
 host once per episode (or gathered to rank 0 over RCCL for multi-GPU runs).
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -165,8 +167,8 @@ class ActingLoop:
                L.ptr(self.inv_t_dev), self.n_envs_total, self.VEC_BLOCK, self.pow_threads, self.env_offset,
                self.step_index, self.seed,
                L.ptr(self.ctx), L.stream())
-        L.call("mzba_record_results", L.ptr(counts), L.ptr(values), L.ptr(self.rec["counts"]),
-               L.ptr(self.rec["values"]), self.B, 0, L.ptr(self.ctx), L.stream())
+        L.call("mzba_record_results", L.ptr(counts), L.ptr(values),
+               ctypes.byref(L.sink(self.rec, self.max_steps, self.H * self.W)), 0, L.ptr(self.ctx), L.stream())
         env.step(self.action, False, self.rec, 0, ctx=self.ctx)
         L.call("mzba_ctx_advance", L.ptr(self.ctx), L.stream())
 

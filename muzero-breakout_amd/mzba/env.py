@@ -151,58 +151,48 @@ class CompactBreakout:
         self.reward = torch.zeros(B, dtype=torch.float32, device=dev)
         self.valid = torch.ones(B, 3, dtype=torch.float32, device=dev)
 
-    def _state_ptrs(self):
-        return (L.ptr(self.paddle), L.ptr(self.bx), L.ptr(self.by), L.ptr(self.dx), L.ptr(self.dy), L.ptr(self.done),
-                L.ptr(self.bricks), self.nw)
+        # the C ABI's view of all of the above (include/mzba.h mzba_env_state): the tensors are never reallocated
+        a = L.addr
+        self._abi = L.EnvState(a(self.paddle), a(self.bx), a(self.by), a(self.dx), a(self.dy), a(self.done),
+                               a(self.bricks), self.nw, a(self.cur_frame), a(self.cur_src), a(self.hist_frames),
+                               a(self.hist_actions), a(self.hist_len), L_hist, B, height, width, paddle_width,
+                               brick_rows)
+        self._env = ctypes.byref(self._abi)
 
     def reset(self, episode, params=None):
         pr = None
         if params is not None:
             pr = torch.as_tensor(np.asarray(params, dtype=np.int32), device=self.device).contiguous()
-        L.call("mzba_env_reset_compact", *self._state_ptrs(), L.ptr(self.cur_frame), L.ptr(self.cur_src),
-               L.ptr(self.hist_frames),
-               L.ptr(self.hist_actions), L.ptr(self.hist_len), self.Lh, self.B, self.H, self.W, self.pw,
-               self.brick_rows, self.seed, episode, self.env_offset, L.ptr(pr), self.pad_action, L.stream())
+        L.call("mzba_env_reset_compact", self._env, self.seed, episode, self.env_offset, L.ptr(pr), self.pad_action,
+               L.stream())
         self.valid.fill_(1.0)
 
     def restart(self, start, ctx, blk, params=None):
         """Streaming acting: reset in place every env that is done or holds blk[1] records, under the
         episode key blk[0] + ctx[2], and write row ctx[2] of `start` (u32 (T, B) start words as int32;
         include/mzba.h). `params`: device int32 (4, B) in place of the keyed draws."""
-        L.call("mzba_env_restart_compact", *self._state_ptrs(), L.ptr(self.cur_frame), L.ptr(self.cur_src),
-               L.ptr(self.hist_frames), L.ptr(self.hist_actions), L.ptr(self.hist_len), self.Lh, L.ptr(start),
-               L.ptr(ctx), L.ptr(blk), self.B, self.H, self.W, self.pw, self.brick_rows, self.seed, self.env_offset,
-               L.ptr(params), self.pad_action, L.stream())
+        L.call("mzba_env_restart_compact", self._env, L.ptr(start), L.ptr(ctx), L.ptr(blk), self.seed,
+               self.env_offset, L.ptr(params), self.pad_action, L.stream())
 
     def step(self, action, first_step, rec=None, t=0, ctx=None):
         """action: int64 (B,) device. rec: optional sink dict of (T,B,...) buffers, row t; with a
         device step context `ctx` the row (and first_step) are read on the device instead."""
-        ra = rr = rm = rf = None
+        sk = None
         if rec is not None:
-            if ctx is not None:
-                ra, rr, rm, rf = rec["action"], rec["reward"], rec["mask"], rec.get("frame")
-            else:
-                ra, rr, rm = rec["action"][t], rec["reward"][t], rec["mask"][t]
-                rf = rec["frame"][t] if rec.get("frame") is not None else None
-        L.call("mzba_env_step_compact", *self._state_ptrs(), L.ptr(action), L.ptr(self.reward), L.ptr(self.valid),
-               L.ptr(self.cur_frame), L.ptr(self.cur_src), L.ptr(self.hist_frames), L.ptr(self.hist_actions),
-               L.ptr(self.hist_len), self.Lh, L.ptr(ra), L.ptr(rr), L.ptr(rm), L.ptr(rf), 1 if first_step else 0, self.B, self.H, self.W, self.pw,
-               self.brick_rows, self.rewards4, L.ptr(ctx), self.rec_flags, L.stream())
+            sk = ctypes.byref(L.sink(rec, rec["action"].shape[0], self.H * self.W, None if ctx is not None else t))
+        L.call("mzba_env_step_compact", self._env, L.ptr(action), L.ptr(self.reward), L.ptr(self.valid), sk,
+               1 if first_step else 0, self.rewards4, L.ptr(ctx), self.rec_flags, L.stream())
 
     def to_planes(self):
         planes = torch.empty(self.B, 3, self.H, self.W, dtype=torch.float32, device=self.device)
-        L.call("mzba_compact_to_planes", L.ptr(self.paddle), L.ptr(self.bx), L.ptr(self.by), L.ptr(self.done),
-               L.ptr(self.bricks), self.nw, L.ptr(planes), self.B, self.H, self.W, self.pw, self.brick_rows, L.stream())
+        L.call("mzba_compact_to_planes", self._env, L.ptr(planes), L.stream())
         return planes
 
     def build_rep_input(self, out, cs, bf16):
-        L.call("mzba_build_rep_input", L.ptr(self.cur_frame), L.ptr(self.cur_src), L.ptr(self.hist_frames),
-               L.ptr(self.hist_actions), L.ptr(self.hist_len), self.Lh, L.ptr(out), 1 if bf16 else 0, self.B,
-               self.H * self.W, cs, L.stream())
+        L.call("mzba_build_rep_input", self._env, L.ptr(out), 1 if bf16 else 0, cs, L.stream())
 
     def current_frame(self):
         """Every env's current u8 gray-code frame, (B*H*W,) on the device."""
         out = torch.empty(self.B * self.H * self.W, dtype=torch.uint8, device=self.device)
-        L.call("mzba_env_current_frame", L.ptr(self.cur_frame), L.ptr(self.cur_src), L.ptr(self.hist_frames),
-               L.ptr(self.hist_len), self.Lh, L.ptr(out), self.B, self.H * self.W, L.stream())
+        L.call("mzba_env_current_frame", self._env, L.ptr(out), L.stream())
         return out

@@ -12,6 +12,8 @@ return device tensors with the reference's dtypes and shapes.
 priority array beside the ring, set at ingest from |searched value - n-step target|, a device sampler
 (`sample`) and the learner's write-back (`update_priorities`). Off by default; nothing else changes.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -40,6 +42,8 @@ class DeviceReplayBuffer:
             "targets": torch.zeros(cap, K, dtype=torch.float32, device=dev),
             "reward_sum": torch.zeros(cap, dtype=torch.float32, device=dev),
         }
+        # the C ABI's view of the ring (include/mzba.h mzba_replay_ring): the rows are never reallocated
+        self._abi = L.ReplayRing(*(self._ring[k].data_ptr() for k, _ in L.ReplayRing._fields_[:8]), cap, K, seq_len)
         self._lut = torch.from_numpy(gray_lut()).to(dev)
         self.start = 0      # ring slot of the oldest window
         self.length = 0     # windows stored (replay_buffer.py:87)
@@ -76,22 +80,15 @@ class DeviceReplayBuffer:
         lens = torch.empty(B, dtype=torch.int32, device=dev)
         rsum = torch.empty(B, dtype=torch.float32, device=dev)
         offs = torch.empty(B + 1, dtype=torch.int32, device=dev)
-        args = (L.ptr(rec["action"]), L.ptr(rec["reward"]), L.ptr(rec["mask"]), L.ptr(rec["counts"]),
-                L.ptr(rec["values"]), L.ptr(rec["frame"]), L.ptr(frame0), T, B, HW)
-        L.call("mzba_replay_plan", *args, self.K, min_len, L.ptr(lens), L.ptr(rsum), L.ptr(offs), L.stream())
+        sk = ctypes.byref(L.sink(rec, T, HW))
+        L.call("mzba_replay_plan", sk, L.ptr(frame0), self.K, min_len, L.ptr(lens), L.ptr(rsum), L.ptr(offs),
+               L.stream())
         n = int(offs[B].item())
-        self._write(args, lens, rsum, offs, n, T)
-        return n
-
-    def _write(self, args, lens, rsum, offs, n, T):
-        cap = self.max_length
-        head = (self.start + self.length) % cap
-        g = self._ring
-        L.call("mzba_replay_write", *args, L.ptr(lens), L.ptr(rsum), L.ptr(offs), n, L.ptr(g["past_actions"]),
-               L.ptr(g["future_actions"]), L.ptr(g["states"]), L.ptr(g["rewards"]), L.ptr(g["counts"]),
-               L.ptr(g["values"]), L.ptr(g["targets"]), L.ptr(g["reward_sum"]), cap, head, self.K,
-               self.hist_seq_len, L.ptr(self._powers(T)), L.stream())
+        head = (self.start + self.length) % self.max_length
+        L.call("mzba_replay_write", sk, L.ptr(frame0), L.ptr(lens), L.ptr(rsum), L.ptr(offs), n,
+               ctypes.byref(self._abi), head, L.ptr(self._powers(T)), L.stream())
         self._commit(head, n)
+        return n
 
     def _commit(self, head, n):
         """The ring's bookkeeping after n windows were written from slot `head` on (the newest max_length kept)."""
@@ -122,18 +119,13 @@ class DeviceReplayBuffer:
         cnt = torch.empty(B, 2, dtype=torch.int32, device=dev)
         offs = torch.empty(B + 1, 2, dtype=torch.int32, device=dev)
         table = torch.empty(6, nmax + 1, dtype=torch.int32, device=dev)
-        L.call("mzba_replay_stream_plan", L.ptr(rec["reward"]), L.ptr(rec["mask"]), L.ptr(rec["start"]), L.ptr(done),
-               L.ptr(hlen), T, B, self.K, min_len, int(episode_cap), 1 if tail == "keep" else 0, L.ptr(cnt),
-               L.ptr(offs), L.ptr(table), nmax, L.stream())
+        sk = ctypes.byref(L.sink(rec, T, self.H * self.W))
+        L.call("mzba_replay_stream_plan", sk, L.ptr(done), L.ptr(hlen), self.K, min_len, int(episode_cap),
+               1 if tail == "keep" else 0, L.ptr(cnt), L.ptr(offs), L.ptr(table), nmax, L.stream())
         nseg, n = offs[B].tolist()
-        cap = self.max_length
-        head = (self.start + self.length) % cap
-        g = self._ring
-        L.call("mzba_replay_stream_write", L.ptr(rec["action"]), L.ptr(rec["reward"]), L.ptr(rec["counts"]),
-               L.ptr(rec["values"]), L.ptr(rec["frame"]), T, B, self.H, self.W, paddle_width, brick_rows, L.ptr(table),
-               nmax, nseg, n, L.ptr(g["past_actions"]), L.ptr(g["future_actions"]), L.ptr(g["states"]),
-               L.ptr(g["rewards"]), L.ptr(g["counts"]), L.ptr(g["values"]), L.ptr(g["targets"]),
-               L.ptr(g["reward_sum"]), cap, head, self.K, self.hist_seq_len, L.ptr(self._powers(T)), L.stream())
+        head = (self.start + self.length) % self.max_length
+        L.call("mzba_replay_stream_write", sk, self.H, self.W, paddle_width, brick_rows, L.ptr(table), nmax, nseg, n,
+               ctypes.byref(self._abi), head, L.ptr(self._powers(T)), L.stream())
         self._commit(head, n)
         # a segment of L records gives L - K + 1 windows: the kept rows are windows + segments * (K - 1)
         self.last_stream = {"segments": nseg, "windows": n}

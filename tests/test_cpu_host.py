@@ -26,6 +26,99 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.exported_symbols()) == decl
 
 
+_CTYPE = {"int": "I", "long long": "LL", "int64_t": "LL", "uint64_t": "U64", "uint32_t": "U32", "float": "F",
+          "double": "D"}
+
+
+def _prototypes():
+    """{name: (return type, [parameter type, ...])} of every mzba_* function declared in include/mzba.h."""
+    h = open(os.path.join(ROOT, "include", "mzba.h")).read()
+    h = re.sub(r"/\*.*?\*/", " ", h, flags=re.S)
+    h = re.sub(r"//[^\n]*|^\s*#[^\n]*", " ", h, flags=re.M)
+    out = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w ]*?)\s*\b(mzba_\w+)\s*\(([^()]*)\)\s*;", h):
+        assert name not in out, name
+        params = [" ".join(p.split()) for p in params.split(",")]
+        out[name] = (" ".join(ret.split()), [] if params == ["void"] else params)
+    return out
+
+
+def _param_code(p):
+    if "*" in p or p.startswith("hipStream_t "):
+        return "P"
+    ctype = p.rsplit(" ", 1)[0]  # without the parameter's name
+    assert ctype in _CTYPE, f"parameter type the table's check does not know: {p!r}"
+    return _CTYPE[ctype]
+
+
+def test_signature_table_matches_header_types():
+    """Every prototype of include/mzba.h against _lib.SIGNATURES, parameter by parameter (pointers and the stream are
+    P), and the non-int return types against _lib.RESTYPES: the table ctypes converts by is the header's."""
+    from mzba import _lib
+    protos = _prototypes()
+    assert sorted(protos) == _declared()
+    for name, (ret, params) in protos.items():
+        got = [getattr(_lib, _param_code(p)) for p in params]
+        assert got == _lib.SIGNATURES[name], (name, params)
+        assert _lib.RESTYPES.get(name, _lib.I) is getattr(_lib, _CTYPE[ret]), (name, ret)
+    assert set(_lib.RESTYPES) <= set(protos)
+
+
+def test_struct_sizes_match_the_library():
+    import ctypes
+    from mzba import _lib
+    L = _lib.lib()
+    assert sorted(_lib.STRUCTS) == ["mzba_env_state", "mzba_replay_ring", "mzba_sink", "mzba_tower_ext",
+                                    "mzba_tree_step"]
+    for name, cls in _lib.STRUCTS.items():
+        assert L.mzba_struct_bytes(name.encode()) == ctypes.sizeof(cls), name
+    assert L.mzba_struct_bytes(b"mzba_guard") == -1
+    assert L.mzba_struct_bytes(None) == -1
+
+
+def test_env_and_replay_entry_points_reject_bad_arguments_without_gpu():
+    """The entry points that take the env state, the sink and the ring check them before any HIP call: a NULL
+    required struct and an empty batch (B = 0) return -1; the streamed plan keeps its -2 for a short table."""
+    from ctypes import byref, c_void_p
+    from mzba import _lib
+    L = _lib.lib()
+    p = c_void_p(4096)
+    a = 4096
+
+    def env(B=3):
+        return byref(_lib.EnvState(*[a] * 7, 1, *[a] * 5, 4, B, 16, 20, 6, 3))
+
+    def sink(B=3, T=8):
+        return byref(_lib.Sink(*[a] * 7, T, B, 320))
+
+    ring = byref(_lib.ReplayRing(*[a] * 8, 64, 5, 4))
+    r4 = (_lib.F * 4)(1, 1, -1, 1)
+    calls = {
+        "mzba_env_reset_compact": lambda e, s, g: (e, 0, 0, 0, None, 0, None),
+        "mzba_env_restart_compact": lambda e, s, g: (e, p, p, p, 0, 0, None, 0, None),
+        "mzba_env_step_compact": lambda e, s, g: (e, p, p, p, None, 1, r4, None, 0, None),
+        "mzba_compact_to_planes": lambda e, s, g: (e, p, None),
+        "mzba_build_rep_input": lambda e, s, g: (e, p, 1, 64, None),
+        "mzba_env_current_frame": lambda e, s, g: (e, p, None),
+        "mzba_replay_plan": lambda e, s, g: (s, p, 5, 6, p, p, p, None),
+        "mzba_replay_write": lambda e, s, g: (s, p, p, p, p, 4, g, 0, p, None),
+        "mzba_replay_stream_plan": lambda e, s, g: (s, p, p, 5, 6, 261, 0, p, p, p, 64, None),
+        "mzba_replay_stream_write": lambda e, s, g: (s, 16, 20, 6, 3, p, 64, 1, 4, g, 0, p, None),
+    }
+    for name, args in calls.items():
+        fn = getattr(L, name)
+        assert fn(*args(None, None, ring)) == -1, name                 # the NULL env state / sink
+        assert fn(*args(env(B=0), sink(B=0), ring)) == -1, name        # B = 0
+    for name in ("mzba_replay_write", "mzba_replay_stream_write"):
+        assert getattr(L, name)(*calls[name](None, sink(), None)) == -1, name  # the NULL ring
+    assert L.mzba_record_results(p, p, None, 0, None, None) == -1
+    assert L.mzba_record_results(p, p, sink(B=0), 0, None, None) == -1
+    # nmax below B * (T / keep): T = 8, keep = max(min_len + 1, K) = 4 -> 3 * 2 = 6 table rows at least
+    plan = lambda nmax: L.mzba_replay_stream_plan(sink(), p, p, 4, 3, 261, 0, p, p, p, nmax, None)  # noqa: E731
+    assert plan(5) == -2
+    assert plan(-1) == -2
+
+
 def test_node_layout_is_one_line():
     from mzba import _lib
     assert _lib.lib().mzba_mcts_node_bytes() == 64
