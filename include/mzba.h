@@ -541,6 +541,37 @@ int mzba_mcts_results(void* nodes, float* root_sum, uint32_t* calls, int32_t* le
                       int env_offset, int search_id, uint64_t seed, const int32_t* ctx, int64_t* counts, float* values,
                       hipStream_t stream);
 
+/* ---- Gumbel search (csrc/gumbel.hip; opt-in, cfg["search"]["kind"] == "gumbel") -----------
+ * The same trees as the entry points above (the tree fields of mzba_tree_step; sqrt_tab, c_tab and calls are not
+ * read), with each node's own value V kept as f32 bits in the node's 4 spare bytes. Root actions are sampled
+ * without replacement (the top m of g + log P) and visited by sequential halving along seq; interior nodes take
+ * the deterministic improved-policy rule; every argmax takes the lowest index on a tie. */
+typedef struct mzba_gumbel {
+  float* g;               /* f32 [B][3] gumbel_scale * variate, written by the root launch */
+  uint8_t* considered;    /* u8 [B] bit a set: action a is in the considered set (root launch) */
+  const int32_t* seq;     /* i32 [S] (device) root visit schedule: simulation s visits a considered action with
+                             N == seq[s] (built on the host, mzba.search.gumbel_schedule) */
+  int m;                  /* considered actions, 2 or 3 */
+  float c_visit, c_scale, gumbel_scale;
+} mzba_gumbel;
+
+/* Root: variates z = g_in (f32 [B][3]) or -log(-log u_a), u_a = ((x_a >> 8) + 0.5) / 2^24 from Philox (env +
+ * env_offset, stream 5, search id, a), written to g_out (optional); gm->g = gumbel_scale * z, the considered mask,
+ * the root node (P = pi_root, V = v_root) and simulation 0's selection (its child linked to slot 1). Every entry
+ * point returns -1 for a NULL struct or required buffer, B <= 0, S <= 0 or m outside {2, 3}. */
+int mzba_gumbel_root(const mzba_tree_step* ts, const mzba_gumbel* gm, const float* v_root, const float* pi_root,
+                     const float* g_in, float* g_out, hipStream_t stream);
+/* One launch per simulation ts->sim: its backup (as mzba_mcts_backup, with ts->r, ts->gamma, decoded v[B] and
+ * pi[B][3] of the new node, whose V = v) and, when sim + 1 < S, the selection of simulation sim + 1. */
+int mzba_gumbel_step(const mzba_tree_step* ts, const mzba_gumbel* gm, const float* v, const float* pi,
+                     hipStream_t stream);
+/* action i64[B] = the most visited considered action (largest g + log P + sigma among equals); values f32[B] = the
+ * improved policy's value sum pi'_a cq_a; counts i64[B][3] = llrint(pi'_a 2^24), pi' = softmax(log P + sigma) at the
+ * root, a fixed-point policy target the sink, the ingest and the ring's f32 row carry exactly; root_n (optional)
+ * i32[B][3] = the root's visit counts. */
+int mzba_gumbel_results(const mzba_tree_step* ts, const mzba_gumbel* gm, int64_t* counts, float* values,
+                        int64_t* action, int32_t* root_n, hipStream_t stream);
+
 /* Temperature sampling (train_torch.py:191-198 `visit_counts ** (1/self.temperature)` / sum(dim=1) then
  * Categorical(probs[i]).sample()): probs bit-identical to torch's CPU evaluation on the reference's whole
  * (n_envs_total, 3) int64 batch tensor (csrc/torch_pow.h: SLEEF powf_u10 on the vectorized part, f32(pow(double))
@@ -768,7 +799,7 @@ int mzba_replay_priority_update_g(float* q, const int32_t* slots, const float* t
                                   float eps, const mzba_guard_block* block, hipStream_t stream);
 
 /* sizeof of an ABI struct by its name (mzba_env_state, mzba_sink, mzba_replay_ring, mzba_tower_ext,
- * mzba_tree_step), -1 for another name: a binding checks its mirror of each struct against it when it loads. */
+ * mzba_tree_step, mzba_gumbel), -1 for another name: a binding checks its mirror of each struct against it when it loads. */
 int mzba_struct_bytes(const char* name);
 
 #ifdef __cplusplus

@@ -90,6 +90,10 @@ SIGNATURES = {
     "mzba_mcts_select": [P, P, P, P, P, P, P, P, P, I, I, I, I, U64, P, I, P],
     "mzba_mcts_backup": [P, P, P, P, P, P, P, P, P, I, I, I, I, U64, P, I, P, P, P, F, P],
     "mzba_mcts_results": [P, P, P, P, P, P, P, P, P, I, I, I, I, U64, P, P, P, P],
+    # Gumbel search (gumbel.hip): the tree as a TreeStep, the mode's state as a Gumbel, both by reference
+    "mzba_gumbel_root": [P, P, P, P, P, P, P],
+    "mzba_gumbel_step": [P, P, P, P, P],
+    "mzba_gumbel_results": [P, P, P, P, P, P, P],
     "mzba_sample_actions": [P, P, P, I, D, P, I, I, I, I, I, U64, P, P],
     "mzba_torch_pow": [P, P, LL, D, LL, LL, I, I, P],
     "mzba_record_results": [P, P, P, I, P, P],
@@ -189,9 +193,17 @@ class ReplayRing(ctypes.Structure):
                 ("values", P), ("targets", P), ("reward_sum", P), ("cap", I), ("K", I), ("hist", I)]
 
 
+class Gumbel(ctypes.Structure):
+    """include/mzba.h mzba_gumbel (the Gumbel search's root state and constants)."""
+    _fields_ = [("g", P), ("considered", P), ("seq", P), ("m", I), ("c_visit", F), ("c_scale", F),
+                ("gumbel_scale", F)]
+
+
 # every struct of the ABI and its mirror here; lib() checks the sizes against mzba_struct_bytes
 STRUCTS = {"mzba_env_state": EnvState, "mzba_sink": Sink, "mzba_replay_ring": ReplayRing, "mzba_tower_ext": TowerExt,
            "mzba_tree_step": TreeStep}
+# the opt-in search mode's struct, checked the same way
+GUMBEL_STRUCTS = {"mzba_gumbel": Gumbel}
 
 # entry points that return something other than a status code
 RESTYPES = {"mzba_tower_ws_bytes": LL, "mzba_tower_plan": I, "mzba_conv_lat_get_variant": I, "mzba_conv_wgrad_ws_bytes": LL,
@@ -214,7 +226,7 @@ def lib():
             fn = getattr(L, name)
             fn.argtypes = argt
             fn.restype = RESTYPES.get(name, ctypes.c_int)
-        for name, cls in STRUCTS.items():
+        for name, cls in {**STRUCTS, **GUMBEL_STRUCTS}.items():
             if L.mzba_struct_bytes(name.encode()) != ctypes.sizeof(cls):
                 raise RuntimeError(f"mzba: {LIB_PATH} was built with another {name} than this binding's "
                                    f"({L.mzba_struct_bytes(name.encode())} bytes, {ctypes.sizeof(cls)} here)")

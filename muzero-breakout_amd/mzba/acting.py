@@ -52,7 +52,12 @@ class ObservationTrajectory:
 
 
 class ActingLoop:
-    """B envs acting with MCTS on one device. `env_offset` = global id of env 0 (sharding)."""
+    """B envs acting with MCTS on one device. `env_offset` = global id of env 0 (sharding).
+
+    With cfg["search"]["kind"] == "gumbel"  the step's action is the search's chosen action:
+    the temperature sampling kernel is not launched, so `temperature` has no effect, and no Dirichlet noise is
+    mixed into the root. The sink's `counts` rows then hold the improved policy in 24-bit fixed point and its
+    `values` the improved policy's value; `inject_noise` / `noise_log` serve the root's Gumbel variates."""
 
     MAX_STEPS = 261  # train_torch.py:186 `length_counter > 260`
 
@@ -99,7 +104,9 @@ class ActingLoop:
         if self.rep_agent.packed.tdt != p.tdt or self.rep_agent.device != dev:
             raise ValueError("rep_agent must share the search agent's device and dtype")
         self.rep_runner = self.rep_agent.runner(B, height, width)
-        self.action = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.gumbel = self.search.kind == "gumbel"
+        # Gumbel mode: the action buffer is the search's chosen action
+        self.action = self.ws.gumbel.actions if self.gumbel else torch.zeros(B, dtype=torch.int64, device=dev)
         T = max_steps
         self.rec = {
             "action": torch.zeros(T, B, dtype=torch.uint8, device=dev),
@@ -162,15 +169,22 @@ class ActingLoop:
         # _prepare_mcts_input + create_hidden_state_root -> pool slot 0
         env.build_rep_input(self.rep_in, self.cs, self.agent.dtype == "bf16")
         self.rep_runner.representation(self.rep_in, ws.cur, pool=ws.pool, pool_env_stride=(ws.S + 1) * n)
-        values, counts = ws.run(self.search_id, self._noise_in, ctx=self.ctx, w_dev=self.root_w_dev)
-        L.call("mzba_sample_actions", L.ptr(counts), L.ptr(self.action), None, self.B, 1.0 / self.temperature,
-               L.ptr(self.inv_t_dev), self.n_envs_total, self.VEC_BLOCK, self.pow_threads, self.env_offset,
-               self.step_index, self.seed,
-               L.ptr(self.ctx), L.stream())
+        if self.gumbel:
+            values, counts, _ = ws.run_gumbel(self.search_id, self._noise_in, ctx=self.ctx)
+        else:
+            values, counts = ws.run(self.search_id, self._noise_in, ctx=self.ctx, w_dev=self.root_w_dev)
+            self._sample(counts)
         L.call("mzba_record_results", L.ptr(counts), L.ptr(values),
                ctypes.byref(L.sink(self.rec, self.max_steps, self.H * self.W)), 0, L.ptr(self.ctx), L.stream())
         env.step(self.action, False, self.rec, 0, ctx=self.ctx)
         L.call("mzba_ctx_advance", L.ptr(self.ctx), L.stream())
+
+    def _sample(self, counts):
+        """Temperature sampling of the step's action from the visit counts (train_torch.py:191-198)."""
+        L.call("mzba_sample_actions", L.ptr(counts), L.ptr(self.action), None, self.B, 1.0 / self.temperature,
+               L.ptr(self.inv_t_dev), self.n_envs_total, self.VEC_BLOCK, self.pow_threads, self.env_offset,
+               self.step_index, self.seed,
+               L.ptr(self.ctx), L.stream())
 
     def capture(self):
         """Capture one acting step (~S x 65 launches) into a HIP graph; act() then replays it.
@@ -202,7 +216,7 @@ class ActingLoop:
         else:
             self._act_body()
             if self.noise_log is not None:
-                self.noise_log.append(self.ws.tree.noise.clone())
+                self.noise_log.append((self.ws.gumbel.variates if self.gumbel else self.ws.tree.noise).clone())
         self.search_id += 1
         self.step_index += 1
         self.t += 1
@@ -260,7 +274,10 @@ def run_test_simulation(cfg, agent, batch=2, seed=0, episode=0, max_steps_test=2
     root representation's (self.mu_zero, the learner net, :567; default: `agent`). Returns
     (ObservationTrajectory per env, frames per env: the grayscale (1, H, W) frames of the steps
     after which the env was still live — what the reference logs — and the loop). The reference
-    writes the frames of env 0 to tensorboard; logging is left to the caller."""
+    writes the frames of env 0 to tensorboard; logging is left to the caller. Always the PUCT search, whatever
+    cfg["search"]["kind"] says."""
+    if cfg["search"].get("kind", "puct") != "puct":
+        cfg = {**cfg, "search": {**cfg["search"], "kind": "puct"}}
     loop = ActingLoop(cfg, agent, batch, seed=seed, temperature=temperature, max_steps=max_steps_test + 1,
                       pad_action=1, rec_flags=3, rep_agent=rep_agent)
     loop.noise_log = [] if log_noise else None

@@ -7,7 +7,12 @@ simulation and selects the next leaf (`prediction_tree_`); unfused, one select k
 prediction net and one backup kernel.
 The launch sequence is identical for every call of a given (B, S), so the acting loop
 can capture it in a HIP graph.
+
+cfg["search"]["kind"] == "gumbel" selects the Gumbel search (csrc/gumbel.hip): per
+simulation the dynamics step, the prediction step without a tree and one tree launch (backup +
+next selection). An absent key or "puct" is the path above.
 """
+import ctypes
 import math
 import os
 
@@ -24,6 +29,76 @@ def ucb_tables(S, c1, c2, device):
     sq = np.array([math.sqrt(n) for n in range(S + 1)], dtype=np.float64).astype(np.float32)
     ct = np.array([c1 + math.log((n + c2 + 1) / c2) for n in range(S + 1)], dtype=np.float64).astype(np.float32)
     return torch.from_numpy(sq).to(device), torch.from_numpy(ct).to(device)
+
+
+def gumbel_schedule(S, m):
+    """The root visit schedule seq[0..S) of sequential halving over m considered actions:
+    simulation s visits a considered action whose visit count is seq[s]."""
+    l2 = max(1, math.ceil(math.log2(m)))
+    visits = [0] * m
+    nc = m
+    seq = []
+    while len(seq) < S:
+        extra = max(1, int(S / (l2 * nc)))
+        for _ in range(extra):
+            seq += visits[:nc]
+            for i in range(nc):
+                visits[i] += 1
+        nc = max(2, nc // 2)
+    return seq[:S]
+
+
+def gumbel_params(cfg):
+    """(max_considered, c_visit, c_scale, scale) of cfg["search"]["gumbel"] with the defaults 3, 50, 1, 1."""
+    g = cfg["search"].get("gumbel", {})
+    m = int(g.get("max_considered", 3))
+    if m not in (2, 3):
+        raise ValueError(f"gumbel search: max_considered must be 2 or 3, not {m}")
+    return m, float(g.get("c_visit", 50.0)), float(g.get("c_scale", 1.0)), float(g.get("scale", 1.0))
+
+
+def search_kind(cfg):
+    kind = cfg["search"].get("kind", "puct")
+    if kind not in ("puct", "gumbel"):
+        raise ValueError(f"cfg['search']['kind'] must be 'puct' or 'gumbel', not {kind!r}")
+    return kind
+
+
+class GumbelState:
+    """Device buffers of the Gumbel search over a TreeState's trees, and its three launches."""
+
+    def __init__(self, tree, m, c_visit, c_scale, scale, device):
+        self.tree = tree
+        B, S = tree.B, tree.S
+        self.m, self.c_visit, self.c_scale, self.scale = m, c_visit, c_scale, scale
+        self.g = torch.empty(B, 3, dtype=torch.float32, device=device)
+        self.considered = torch.empty(B, dtype=torch.uint8, device=device)
+        self.seq = torch.tensor(gumbel_schedule(S, m), dtype=torch.int32, device=device)
+        self.variates = torch.empty(B, 3, dtype=torch.float32, device=device)  # the root's standard Gumbel draws
+        self.actions = torch.empty(B, dtype=torch.int64, device=device)
+        self.root_n = torch.empty(B, 3, dtype=torch.int32, device=device)
+
+    def _structs(self, ta, sim=0, gamma=0.0, r=None):
+        t = self.tree
+        env_offset, search_id, seed, ctx = ta
+        ts = L.TreeStep(L.addr(t.nodes), L.addr(t.root_sum), L.addr(t.calls), L.addr(t.leaf_parent),
+                        L.addr(t.leaf_action), L.addr(t.depth), L.addr(t.path), L.addr(t.sqrt_tab), L.addr(t.c_tab),
+                        t.B, t.S, env_offset, search_id, seed, L.addr(ctx), sim, gamma, L.addr(r))
+        gm = L.Gumbel(L.addr(self.g), L.addr(self.considered), L.addr(self.seq), self.m, self.c_visit, self.c_scale,
+                      self.scale)
+        return ctypes.byref(ts), ctypes.byref(gm)
+
+    def root(self, ta, v_root, pi_root, g_in=None):
+        L.call("mzba_gumbel_root", *self._structs(ta), L.ptr(v_root), L.ptr(pi_root), L.ptr(g_in),
+               L.ptr(self.variates), L.stream())
+
+    def step(self, ta, sim, r, v, pi, gamma):
+        L.call("mzba_gumbel_step", *self._structs(ta, sim, gamma, r), L.ptr(v), L.ptr(pi), L.stream())
+
+    def results(self, ta):
+        t = self.tree
+        L.call("mzba_gumbel_results", *self._structs(ta), L.ptr(t.counts), L.ptr(t.values), L.ptr(self.actions),
+               L.ptr(self.root_n), L.stream())
 
 
 class TreeState:
@@ -69,6 +144,9 @@ class MCTSSearchVec:
 
     search(hidden_state (B,C,h,w), action_mask (B,3), training_iteration)
       -> (values f32[B] CPU, visit_counts i64[B,3] CPU), like mcts.py:71.
+    In Gumbel mode (cfg["search"]["kind"] == "gumbel") the second result is the improved policy in 24-bit
+    fixed point (rows sum to 2^24 within rounding), the first its value, and the chosen actions are kept
+    in `self.selected_actions` (i64[B] CPU); `noise` then injects the root's Gumbel variates.
     `action_mask` and `training_iteration` are accepted and ignored, as in the
     reference (mcts.py:124,157 use ones_like(action_mask)).
     Randomness: Dirichlet root noise and ucb tie-breaks come from the keyed Philox
@@ -89,6 +167,9 @@ class MCTSSearchVec:
         self.seed = seed
         self.env_offset = env_offset
         self.search_id = 0
+        self.kind = search_kind(cfg)
+        self.gumbel = gumbel_params(cfg) if self.kind == "gumbel" else None
+        self.selected_actions = None
         self._ws = {}
 
     # workspace per (B, agent) -------------------------------------------------------------
@@ -104,9 +185,13 @@ class MCTSSearchVec:
         B = hidden_state.shape[0]
         ws = self.workspace(B)
         ws.load_root(hidden_state)
-        if noise is not None:  # injected Dirichlet rows (B, 3), any array-like
+        if noise is not None:  # injected Dirichlet rows (Gumbel mode: variates) (B, 3), any array-like
             noise = torch.as_tensor(np.asarray(noise, dtype=np.float32), device=ws.agent.device).contiguous()
-        values, counts = ws.run(self.search_id, noise)
+        if self.kind == "gumbel":
+            values, counts, actions = ws.run_gumbel(self.search_id, noise)
+            self.selected_actions = actions.cpu()
+        else:
+            values, counts = ws.run(self.search_id, noise)
         self.search_id += 1
         return values.cpu(), counts.cpu()
 
@@ -129,6 +214,7 @@ class SearchWorkspace:
         self.v = torch.empty(B, dtype=torch.float32, device=dev)
         self.pi = torch.empty(B, 3, dtype=torch.float32, device=dev)
         self.runner = agent.runner(B, p.lh * 4, p.lw * 4)
+        self.gumbel = GumbelState(self.tree, *search.gumbel, dev) if search.gumbel is not None else None
         # backup + next select ride on the fused prediction launch (MZBA_TREE_FUSION=0: separate kernels)
         self.use_tree_fusion = os.environ.get("MZBA_TREE_FUSION", "1") != "0"
         # fused steps: latents straight from / to their node-pool slots (MZBA_POOL_SLOTS=0: through `cur`,
@@ -178,6 +264,39 @@ class SearchWorkspace:
         self.tree.results(ta)
         return self.tree.values, self.tree.counts
 
+    def run_gumbel(self, search_id, g=None, ctx=None, record=None):
+        """The Gumbel search on the device; root latent in pool slot 0. Returns (values, the
+        improved policy in 24-bit fixed point i64[B][3], chosen actions i64[B]). `g` (device f32 [B][3]) injects
+        the root's Gumbel variates in place of the device draw; `ctx` as in run(). Per simulation: the dynamics
+        step, the prediction step without a tree, one tree launch (backup + the next selection). `record` (a
+        dict, tests) receives copies of the decoded network outputs: v_root, pi_root and lists r, v, pi by
+        simulation, what replay_search_gumbel takes."""
+        s, gs = self.s, self.gumbel
+        if gs is None:
+            raise RuntimeError("run_gumbel: the search was not configured with cfg['search']['kind'] == 'gumbel'")
+        B, S, n = self.B, self.S, self.n
+        ta = (s.env_offset, search_id, s.seed, ctx)
+        rn = self.runner
+        slots = self.pool.view(B, S + 1, n)
+        direct = rn.fused_ok() and self.use_pool_slots
+        rn.prediction(slots[:, 0] if direct else self._root_copy(slots), self.pi, self.v)
+        if record is not None:
+            record.update(v_root=self.v.clone(), pi_root=self.pi.clone(), r=[], v=[], pi=[])
+        gs.root(ta, self.v, self.pi, g)
+        gamma = float(np.float32(s.discount))
+        env_stride = (S + 1) * n
+        for sim in range(S):
+            rn.dynamics(self.pool, self.tree.leaf_action, None if direct else self.cur, self.r,
+                        slot=self.tree.leaf_parent, env_stride=env_stride, slot_stride=n, pool=self.pool,
+                        pool_env_stride=env_stride, pool_slot=sim + 1)
+            rn.prediction(slots[:, sim + 1] if direct else self.cur, self.pi, self.v)
+            if record is not None:
+                for k, t in (("r", self.r), ("v", self.v), ("pi", self.pi)):
+                    record[k].append(t.clone())
+            gs.step(ta, sim, self.r, self.v, self.pi, gamma)
+        gs.results(ta)
+        return self.tree.values, self.tree.counts, gs.actions
+
     def _root_copy(self, slots):
         """The root latents contiguous in `cur` (the unfused launches read contiguous latents)."""
         self.cur.view(self.B, self.n).copy_(slots[:, 0])
@@ -201,3 +320,28 @@ def replay_search(B, S, cfg, v_root, pi_root, noise, r, v, pi, seed, search_id, 
         t.backup(ta, sim, dv(r[sim]), dv(v[sim]), dv(pi[sim]), gamma)
     t.results(ta)
     return t.values.cpu().numpy(), t.counts.cpu().numpy(), leaf
+
+
+def replay_search_gumbel(B, S, cfg, v_root, pi_root, g, r, v, pi, seed, search_id, env_offset=0, device="cuda"):
+    """The Gumbel tree kernels driven by recorded decoded network outputs, without nets: r / v / pi [S][B](x3) are
+    indexed by simulation. `g` f32 [B][3] injects the root's Gumbel variates (None: the device draw). Returns a dict:
+    values, counts (fixed point), actions, root_n, leaf_parent / leaf_action [S][B], variates, g, considered."""
+    L.require_gpu()
+    t = TreeState(B, S, cfg["search"]["c1"], cfg["search"]["c2"], device)
+    gs = GumbelState(t, *gumbel_params(cfg), device)
+    dv = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a), device=device)  # noqa: E731
+    ta = (env_offset, search_id, seed, None)
+    gs.root(ta, dv(v_root), dv(pi_root), dv(g))
+    gamma = float(np.float32(cfg["search"]["discount_factor"]))
+    lp = torch.empty(S, B, dtype=torch.int32, device=device)
+    la = torch.empty(S, B, dtype=torch.int32, device=device)
+    rd, vd, pd = dv(r), dv(v), dv(pi)
+    for sim in range(S):
+        lp[sim].copy_(t.leaf_parent)
+        la[sim].copy_(t.leaf_action)
+        gs.step(ta, sim, rd[sim], vd[sim], pd[sim], gamma)
+    gs.results(ta)
+    host = lambda x: x.cpu().numpy()  # noqa: E731
+    return dict(values=host(t.values), counts=host(t.counts), actions=host(gs.actions), root_n=host(gs.root_n),
+                leaf_parent=host(lp), leaf_action=host(la), variates=host(gs.variates), g=host(gs.g),
+                considered=host(gs.considered))
