@@ -597,6 +597,36 @@ int mzba_record_results(const int64_t* counts, const float* values, const mzba_s
 /* ctx[0..2] += 1 (end of one captured acting step). */
 int mzba_ctx_advance(int32_t* ctx, hipStream_t stream);
 
+/* ---- Reanalyse (csrc/reanalyse.hip): re-search a recorded sink with the current net ----------
+ * The representation input of acting step t (RLSystem._prepare_mcts_input, train_torch.py:259-293) rebuilt from the
+ * sink alone, for all sink->B envs, in mzba_build_rep_input's layout: NHWC out [B][HW][Cs], f32 or bf16 (out_bf16).
+ * The row is ctx ? ctx[2] : t (ctx: the device step context, so one captured graph serves every row). With
+ * F = (L - 1) x g(s0) (frame0 u8 [B][HW]) followed by the frames of rows 0 .. t - 1 and A = L x pad_action followed by
+ * the actions of rows 0 .. t - 1: channels 0 .. L - 2 = the last L - 1 entries of F, channel L - 1 = the frame of
+ * row t - 1 (g(s0) at t = 0; the newest frame appears twice, as in the reference), channels L .. 2L - 1 = the last L
+ * entries of A, each a / 3 in f32, channels >= 2L zero. This is what the acting loop built at step t for an env with
+ * mask[t][b] != 0; for any other env the output is finite and otherwise unspecified. Reads sink->action, sink->frame
+ * (rows < t only) and frame0. -1: t outside [0, sink->T) (without ctx), HW % 16 != 0, L < 2, Cs < 2L, Cs % 8 != 0,
+ * pad_action outside [0, 3), frame / frame0 / out not 16-byte aligned, a staged image above 64 KiB of LDS (128 bytes
+ * per 8 channels of L, plus 4 Cs + 64: L above about 480). A device row outside [0, sink->T) reads and writes
+ * nothing. */
+int mzba_sink_rep_input(const mzba_sink* sink, const uint8_t* frame0, int L, int pad_action, int t,
+                        const int32_t* ctx, void* out, int out_bf16, int Cs, hipStream_t stream);
+
+/* mzba_record_results for the envs with rec->mask[t][b] != 0 only: the other envs' counts and values at row t keep
+ * what the acting loop left there. -1: t outside [0, rec->T) (without ctx), a NULL mask, counts or values. */
+int mzba_record_results_masked(const int64_t* counts, const float* values, const mzba_sink* rec, int t,
+                               const int32_t* ctx, hipStream_t stream);
+
+/* After mzba_replay_write of a planned sink (same lens, rsum, offsets, n_windows, head) and a change of the sink's
+ * counts and values: windows j in [max(j_first, n_windows - cap), n_windows) again, writing ONLY counts, values and
+ * targets of ring slot (head + j) % cap, with the write's own arithmetic. j_first = the first window of the ingest
+ * that is still live (the caller's bookkeeping): the slot of an evicted window holds a newer one and is not
+ * touched. Reads the sink's reward, counts and values; frame0 is not read. */
+int mzba_replay_rewrite(const mzba_sink* sink, const uint8_t* frame0, const int32_t* lens, const float* rsum,
+                        const int32_t* offsets, int n_windows, int j_first, const mzba_replay_ring* ring, int head,
+                        const float* dpow, hipStream_t stream);
+
 /* ===================== learner: one minibatch of RLSystem._training_stage
  * (train_torch.py:380-407) — _k_step_rollout (:487-528) with train-mode BN, loss_fn (:33-66),
  * backward, torch.optim.Adam(lr, weight_decay=1e-4) (networks.py:268). NHWC activations, dtype

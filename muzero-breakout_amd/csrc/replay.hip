@@ -85,19 +85,22 @@ __global__ __launch_bounds__(PT) void replay_plan_kernel(ReplayRecords r, int K,
 }
 
 // window s of a trajectory of L records whose first record is sink row t0 of env b -> ring row `slot`;
-// frame0_chunk(q) = 16-B chunk q of the trajectory's g(s0)
-template <typename F0>
+// frame0_chunk(q) = 16-B chunk q of the trajectory's g(s0). FULL = false (the reanalyse rewrite): only
+// the fields a new search changes, counts, values and targets, are written, by the same statements
+template <bool FULL = true, typename F0>
 MZ_DEV void write_window(const ReplayRecords& r, const ReplayRing& g, int b, int t0, int s, int L, float rsum,
                          size_t slot, int K, int hist, const float* __restrict__ dpow, F0 frame0_chunk) {
   const int tid = threadIdx.x;
   const size_t B = r.B;
   if (tid < hist) {  // actions[s + tid] of the padded list: 32 zeros, then the records
     const int i = s + tid;
-    g.past_actions[slot * hist + tid] = i < hist ? 0 : (int64_t)r.action[(size_t)(t0 + i - hist) * B + b];
+    if (FULL) g.past_actions[slot * hist + tid] = i < hist ? 0 : (int64_t)r.action[(size_t)(t0 + i - hist) * B + b];
   } else if (tid < hist + K) {
     const int i = tid - hist, t = t0 + s + i;  // records [s, s + K) (the padded lists' [s + 32, s + 32 + K))
-    g.future_actions[slot * K + i] = (int64_t)r.action[(size_t)t * B + b];
-    g.rewards[slot * K + i] = r.reward[(size_t)t * B + b];
+    if (FULL) {
+      g.future_actions[slot * K + i] = (int64_t)r.action[(size_t)t * B + b];
+      g.rewards[slot * K + i] = r.reward[(size_t)t * B + b];
+    }
     g.values[slot * K + i] = r.value[(size_t)t * B + b];
     for (int a = 0; a < 3; ++a) g.counts[(slot * K + i) * 3 + a] = (float)r.counts[((size_t)t * B + b) * 3 + a];
     // n-step target (replay_buffer.py:137-151): bootstrap td_steps = 10 ahead, scaled by
@@ -112,9 +115,10 @@ MZ_DEV void write_window(const ReplayRecords& r, const ReplayRing& g, int b, int
       for (int k = 1; k < L - cur; ++k) v = v + dpow[k] * r.reward[(size_t)(t0 + cur + k) * B + b];
     }
     g.targets[slot * K + i] = v;
-  } else if (tid == hist + K) {
+  } else if (FULL && tid == hist + K) {
     g.reward_sum[slot] = rsum;
   }
+  if (!FULL) return;
   // frames: the padded states list = 31 x g(s0), then the recorded frames
   const int chunks = r.HW / 16;
   uint8_t* dst = g.states + slot * hist * r.HW;
@@ -141,6 +145,23 @@ __global__ __launch_bounds__(256) void replay_write_kernel(ReplayRecords r, Repl
   const uint8_t* f0 = r.frame0 + (size_t)b * r.HW;
   write_window(r, g, b, 0, j - offsets[b], lens[b], rsum[b], ((size_t)head + j) % g.cap, K, hist, dpow,
                [f0](int q) { return *reinterpret_cast<const uint4*>(f0 + q * 16); });
+}
+
+// replay_write_kernel's windows j in [j0, n) again after the sink's counts and values changed: the three fields that
+// follow them, nothing else of the slot
+__global__ __launch_bounds__(256) void replay_rewrite_kernel(ReplayRecords r, ReplayRing g, const int32_t* __restrict__ lens,
+                                                             const float* __restrict__ rsum,
+                                                             const int32_t* __restrict__ offsets, int K, int hist,
+                                                             const float* __restrict__ dpow, int head, int j0) {
+  const int j = j0 + blockIdx.x;
+  int lo = 0, hi = r.B;  // last b with offsets[b] <= j
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (offsets[mid] <= j) lo = mid; else hi = mid;
+  }
+  const int b = lo;
+  write_window<false>(r, g, b, 0, j - offsets[b], lens[b], rsum[b], ((size_t)head + j) % g.cap, K, hist, dpow,
+                      [](int) { return make_uint4(0, 0, 0, 0); });
 }
 
 // ---------------------------------------------------------------- streamed sinks (streaming acting)
@@ -312,6 +333,20 @@ int mzba_replay_write(const mzba_sink* sink, const uint8_t* frame0, const int32_
   if (n_windows == 0) return 0;
   const int j0 = n_windows > ring->cap ? n_windows - ring->cap : 0;  // older windows would be evicted at once
   hipLaunchKernelGGL(replay_write_kernel, dim3(n_windows - j0), dim3(256), 0, stream, records(*sink, frame0),
+                     ring_view(*ring), lens, rsum, offsets, ring->K, ring->hist, dpow, head, j0);
+  MZ_LAUNCH_CHECK();
+  return 0;
+}
+
+int mzba_replay_rewrite(const mzba_sink* sink, const uint8_t* frame0, const int32_t* lens, const float* rsum,
+                        const int32_t* offsets, int n_windows, int j_first, const mzba_replay_ring* ring, int head,
+                        const float* dpow, hipStream_t stream) {
+  MZ_CHECK_ARG(sink && sink->T > 0 && sink->B > 0 && ring_ok(ring, head, n_windows) && j_first >= 0, -1);
+  MZ_CHECK_ARG(dpow && sink->reward && sink->counts && sink->values && lens && rsum && offsets, -1);
+  int j0 = n_windows > ring->cap ? n_windows - ring->cap : 0;  // the windows the write kept
+  if (j_first > j0) j0 = j_first;                              // minus those evicted since
+  if (j0 >= n_windows) return 0;
+  hipLaunchKernelGGL(replay_rewrite_kernel, dim3(n_windows - j0), dim3(256), 0, stream, records(*sink, frame0),
                      ring_view(*ring), lens, rsum, offsets, ring->K, ring->hist, dpow, head, j0);
   MZ_LAUNCH_CHECK();
   return 0;

@@ -98,6 +98,10 @@ SIGNATURES = {
     "mzba_torch_pow": [P, P, LL, D, LL, LL, I, I, P],
     "mzba_record_results": [P, P, P, I, P, P],
     "mzba_ctx_advance": [P, P],
+    # reanalyse (reanalyse.hip; the ring rewrite in replay.hip)
+    "mzba_sink_rep_input": [P, P, I, I, I, P, P, I, I, P],
+    "mzba_record_results_masked": [P, P, P, I, P, P],
+    "mzba_replay_rewrite": [P, P, P, P, P, I, I, P, I, P, P],
     # learner (learn.hip; mzba_conv_wpack / mzba_conv_pack_bf16* in pack.hip, mzba_conv_wgrad* in wgrad.hip)
     "mzba_bn_stats": [I, P, I, I, F, F, P, P, P, P, P, P, LL, P],
     "mzba_bn_apply": [I, P, P, P, I, P, I, I, P],

@@ -12,6 +12,7 @@ return device tensors with the reference's dtypes and shapes.
 priority array beside the ring, set at ingest from |searched value - n-step target|, a device sampler
 (`sample`) and the learner's write-back (`update_priorities`). Off by default; nothing else changes.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -19,6 +20,19 @@ import torch
 
 from . import _lib as L
 from .env import gray_lut
+
+# What `ingest_records` leaves in `last_ingest` for a later `reingest_records`: the ring slot of the
+# ingest's window 0, its window count (evicted-at-once ones included), the serial of window 0 (a count of every
+# window the buffer was given in its epoch, so it only grows) and that epoch (`empty_buffer` starts a new one).
+IngestHandle = collections.namedtuple("IngestHandle", "head n serial epoch")
+
+
+def live_windows(serial, n, written, length):
+    """Which windows of an ingest are still in the ring: the ingest gave windows with serials [serial, serial + n),
+    the ring holds the newest `length` of the `written` windows given so far, serials [written - length, written).
+    -> (j_first, count): the live windows are j in [j_first, j_first + count), count = 0 when none is."""
+    j_first = max(0, written - length - serial)
+    return (j_first, n - j_first) if j_first < n else (n, 0)
 
 
 class DeviceReplayBuffer:
@@ -54,6 +68,10 @@ class DeviceReplayBuffer:
         self.alpha, self.beta, self.prio_eps = float(alpha), float(beta), float(prio_eps)
         self._q = torch.zeros(cap, dtype=torch.float32, device=dev) if self.prioritized else None
         self._sample_ws = {}
+        # reanalyse bookkeeping: windows given to the ring in this epoch, the epoch, the last ingest_records' handle
+        self._written = 0
+        self._epoch = 0
+        self.last_ingest = None
 
     def __len__(self):
         return self.length
@@ -87,14 +105,46 @@ class DeviceReplayBuffer:
         head = (self.start + self.length) % self.max_length
         L.call("mzba_replay_write", sk, L.ptr(frame0), L.ptr(lens), L.ptr(rsum), L.ptr(offs), n,
                ctypes.byref(self._abi), head, L.ptr(self._powers(T)), L.stream())
+        self.last_ingest = IngestHandle(head, n, self._written, self._epoch)
         self._commit(head, n)
         return n
+
+    def reingest_records(self, handle, rec, frame0, T, min_len=None):
+        """After the sink of an earlier `ingest_records` (its `last_ingest` handle, the same rec layout, frame0, T
+        and min_len) had its counts and values refreshed (mzba.reanalyse.Reanalyser): rewrite counts, values and
+        n-step targets of the ingest's windows that are still in the ring, and with prioritized=True their
+        priorities by the ingest rule. Windows evicted since are skipped (their slots hold newer windows); start and
+        length do not change. The same ordering rule as an ingest: none between a sample and its
+        update_priorities. -> windows rewritten (0 for an evicted or pre-empty_buffer handle)."""
+        if handle is None or handle.epoch != self._epoch:
+            return 0
+        j_first, count = live_windows(handle.serial, handle.n, self._written, self.length)
+        if count == 0:
+            return 0
+        min_len = self.K + 1 if min_len is None else min_len
+        B = rec["action"].shape[1]
+        dev = self.device
+        lens = torch.empty(B, dtype=torch.int32, device=dev)
+        rsum = torch.empty(B, dtype=torch.float32, device=dev)
+        offs = torch.empty(B + 1, dtype=torch.int32, device=dev)
+        sk = ctypes.byref(L.sink(rec, T, self.H * self.W))
+        L.call("mzba_replay_plan", sk, L.ptr(frame0), self.K, min_len, L.ptr(lens), L.ptr(rsum), L.ptr(offs),
+               L.stream())
+        n = int(offs[B].item())
+        if n != handle.n:
+            raise ValueError(f"reingest_records: the sink plans {n} windows, the handle's ingest wrote {handle.n}")
+        L.call("mzba_replay_rewrite", sk, L.ptr(frame0), L.ptr(lens), L.ptr(rsum), L.ptr(offs), n, j_first,
+               ctypes.byref(self._abi), handle.head, L.ptr(self._powers(T)), L.stream())
+        if self.prioritized:  # the ingest rule over slots (head + j) % cap, j in [j_first, n)
+            self._init_priorities((handle.head + j_first) % self.max_length, n - j_first)
+        return count
 
     def _commit(self, head, n):
         """The ring's bookkeeping after n windows were written from slot `head` on (the newest max_length kept)."""
         cap = self.max_length
         if self.prioritized:
             self._init_priorities(head, n)
+        self._written += n
         total = self.length + n
         self.length = min(total, cap)
         self.start = (self.start + total - self.length) % cap
@@ -207,6 +257,8 @@ class DeviceReplayBuffer:
 
     def empty_buffer(self):
         self.start = self.length = 0
+        self._written = 0
+        self._epoch += 1  # handles of earlier ingests no longer name windows of this ring
         if self.prioritized:
             self._q.zero_()
 
@@ -325,6 +377,7 @@ class DeviceReplayBuffer:
         put("targets", d["bootstrapped_values"][:n], torch.float32)
         g["reward_sum"][:n].copy_(torch.tensor(np.asarray(d["reward_sums"][:n], np.float32)).to(dev))
         self.start, self.length = 0, n
+        self._written = n
         if self.prioritized:
             if d.get("priorities") is not None:
                 self._q[:n].copy_(torch.as_tensor(d["priorities"], dtype=torch.float32)[:n].to(dev))
