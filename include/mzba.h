@@ -380,26 +380,10 @@ int mzba_tower(const void* in, long long in_env_stride, const int32_t* slot, lon
  * before it and the reward / policy / value heads after it run in the same launch, so one
  * dynamics step and one prediction step are one kernel each (networks.py:151-167, 200-241,
  * 314-328; utils.py:74-81). */
-/* One simulation's tree update folded into the fused prediction step: after the heads, each env's
- * thread backs up this simulation's leaf (mcts.py:203-234) and, when sim + 1 < S, selects the next
- * leaf (mcts.py:136-182). Fields as the mzba_mcts_* tree arguments. */
-typedef struct mzba_tree_step {
-  void* nodes;
-  float* root_sum;
-  uint32_t* calls;
-  int32_t* leaf_parent;
-  int32_t* leaf_action;
-  int32_t* depth;
-  int32_t* path;
-  const float* sqrt_tab;
-  const float* c_tab;
-  int B, S, env_offset, search_id;
-  uint64_t seed;
-  const int32_t* ctx;
-  int sim;
-  float gamma;
-  const float* r;         /* decoded rewards of this simulation's dynamics step [B] */
-} mzba_tree_step;
+/* One simulation's tree update folded into the fused prediction step (mzba_tower_ext.tree): after the heads, each
+ * env's thread backs up simulation tree->sim's leaf (mcts.py:203-234) and, when sim + 1 < S, selects the next
+ * leaf (mcts.py:136-182). The struct is defined with the latent MCTS entry points below. */
+typedef struct mzba_tree_step mzba_tree_step;
 
 /* Pixel-tiled tower (csrc/towerp.hip): the same math as mzba_tower on 16 envs per workgroup with one
  * 16-row MFMA tile per latent pixel (no padding taps issued); same weight packing and I/O layout. */
@@ -507,39 +491,48 @@ int mzba_heads_bf16(int nheads, const void* x0, const void* w0, const float* b0,
                     int dec1, float* logits1, float* out1, float smin, float smax, int B, hipStream_t stream);
 
 /* ---- latent MCTS (src/mcts.py:MCTSSearchVec) ------------------------------------------- */
-/* Every tree entry point takes an optional device step context ctx (int32[3]: search id, step
- * index, episode row); when non-NULL its ctx[0] replaces search_id, so one captured HIP graph
- * replays every search. Tree buffers (device): nodes [B][S+1] x mzba_mcts_node_bytes(), root_sum f32[B], calls u32[B],
- * leaf_parent/leaf_action/depth i32[B], path i32[B][S+1]; sqrt_tab/c_tab f32[S+1] =
- * f32(sqrt(n)), f32(c1 + log((n+c2+1)/c2)) computed in double on the host (mcts.py:285-289). */
-int mzba_mcts_node_bytes(void);
+/* A batch of B search trees with S simulations each, and one step's varying values: what every tree entry point
+ * (these, mzba_gumbel_*, mzba_tower_ext.tree) takes. All buffers are device memory. sqrt_tab / c_tab are computed in
+ * double on the host (mcts.py:285-289). sim, gamma and r are read only where an entry point says so. */
+struct mzba_tree_step {
+  void* nodes;            /* [B][S+1] x mzba_mcts_node_bytes(): slot 0 the root, slot s + 1 the node of simulation s */
+  float* root_sum;        /* f32 [B] */
+  uint32_t* calls;        /* u32 [B] ucb_action call counter (the tie-break stream) */
+  int32_t* leaf_parent;   /* i32 [B] */
+  int32_t* leaf_action;   /* i32 [B] */
+  int32_t* depth;         /* i32 [B] */
+  int32_t* path;          /* i32 [B][S+1] */
+  const float* sqrt_tab;  /* f32 [S+1] f32(sqrt(n)) */
+  const float* c_tab;     /* f32 [S+1] f32(c1 + log((n + c2 + 1) / c2)) */
+  int B, S, env_offset, search_id;
+  uint64_t seed;
+  const int32_t* ctx;     /* optional device step context int32[3] (search id, step index, episode row): ctx[0]
+                             replaces search_id, so one captured HIP graph replays every search */
+  int sim;                /* the simulation of a select / backup / step */
+  float gamma;            /* discount of a backup */
+  const float* r;         /* f32 [B] decoded rewards of this simulation's dynamics step (backup) */
+};
+int mzba_mcts_node_bytes(void);  /* bytes of one tree node */
+
+/* Each entry point returns -1, before any HIP call, for a NULL ts, B <= 0, S <= 0, or a NULL nodes, root_sum, calls,
+ * leaf_parent, leaf_action, depth, path, sqrt_tab or c_tab, and for the NULL buffers and sim ranges named with it. */
 
 /* _initialize_trees + _expand_root_nodes (mcts.py:73-134): root P = f32(w_pol*pi) + f32(w_noise*noise),
  * noise = noise_in or Dirichlet(alpha) from Philox stream 2 (written to noise_out), first ucb_action.
  * w_dev (optional, device f32[2]) replaces (w_pol, w_noise): the train loop's noise_weight schedule
- * (train_torch.py:134-135) then needs no new graph capture. */
-int mzba_mcts_root(void* nodes, float* root_sum, uint32_t* calls, int32_t* leaf_parent, int32_t* leaf_action,
-                   int32_t* depth, int32_t* path, const float* sqrt_tab, const float* c_tab, int B, int S,
-                   int env_offset, int search_id, uint64_t seed, const int32_t* ctx, const float* v_root, const float* pi_root,
-                   const float* noise_in, float* noise_out, float w_pol, float w_noise, const float* w_dev, float alpha,
-                   hipStream_t stream);
+ * (train_torch.py:134-135) then needs no new graph capture. v_root f32[B] and pi_root f32[B][3] are required. */
+int mzba_mcts_root(const mzba_tree_step* ts, const float* v_root, const float* pi_root, const float* noise_in,
+                   float* noise_out, float w_pol, float w_noise, const float* w_dev, float alpha, hipStream_t stream);
 
-/* _select_nodes (mcts.py:136-182) for simulation sim >= 1 (ucb_action :281-298). */
-int mzba_mcts_select(void* nodes, float* root_sum, uint32_t* calls, int32_t* leaf_parent, int32_t* leaf_action,
-                     int32_t* depth, int32_t* path, const float* sqrt_tab, const float* c_tab, int B, int S,
-                     int env_offset, int search_id, uint64_t seed, const int32_t* ctx, int sim, hipStream_t stream);
+/* _select_nodes (mcts.py:136-182) for simulation 1 <= ts->sim < S (ucb_action :281-298). */
+int mzba_mcts_select(const mzba_tree_step* ts, hipStream_t stream);
 
-/* _backup (mcts.py:203-234) with decoded r[B], v[B], pi[B][3] of the expanded leaves. */
-int mzba_mcts_backup(void* nodes, float* root_sum, uint32_t* calls, int32_t* leaf_parent, int32_t* leaf_action,
-                     int32_t* depth, int32_t* path, const float* sqrt_tab, const float* c_tab, int B, int S,
-                     int env_offset, int search_id, uint64_t seed, const int32_t* ctx, int sim, const float* r, const float* v,
-                     const float* pi, float gamma, hipStream_t stream);
+/* _backup (mcts.py:203-234) of simulation 0 <= ts->sim < S with ts->gamma and the decoded ts->r [B], v[B], pi[B][3]
+ * of the expanded leaves (all three required). */
+int mzba_mcts_backup(const mzba_tree_step* ts, const float* v, const float* pi, hipStream_t stream);
 
-/* _compute_results (mcts.py:236-250): counts i64[B][3], values f32[B] = f32(double(root_sum)/S). */
-int mzba_mcts_results(void* nodes, float* root_sum, uint32_t* calls, int32_t* leaf_parent, int32_t* leaf_action,
-                      int32_t* depth, int32_t* path, const float* sqrt_tab, const float* c_tab, int B, int S,
-                      int env_offset, int search_id, uint64_t seed, const int32_t* ctx, int64_t* counts, float* values,
-                      hipStream_t stream);
+/* _compute_results (mcts.py:236-250): counts i64[B][3], values f32[B] = f32(double(root_sum)/S), both required. */
+int mzba_mcts_results(const mzba_tree_step* ts, int64_t* counts, float* values, hipStream_t stream);
 
 /* ---- Gumbel search (csrc/gumbel.hip; opt-in, cfg["search"]["kind"] == "gumbel") -----------
  * The same trees as the entry points above (the tree fields of mzba_tree_step; sqrt_tab, c_tab and calls are not

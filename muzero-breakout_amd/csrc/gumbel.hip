@@ -262,18 +262,12 @@ __global__ void gumbel_results_kernel(TreeArgs t, GumbelArgs ga, int64_t* __rest
   }
 }
 
-TreeArgs tree_args(const mzba_tree_step* ts) {
-  return TreeArgs{(Node*)ts->nodes, ts->root_sum, ts->calls, ts->leaf_parent, ts->leaf_action, ts->depth, ts->path,
-                  ts->sqrt_tab, ts->c_tab, ts->B, ts->S, ts->env_offset, ts->search_id, ts->seed, ts->ctx};
-}
-
 GumbelArgs gumbel_args(const mzba_gumbel* gm) {
   return GumbelArgs{gm->g, gm->considered, gm->seq, gm->m, gm->c_visit, gm->c_scale, gm->gumbel_scale};
 }
 
 bool gumbel_ok(const mzba_tree_step* ts, const mzba_gumbel* gm) {
-  return ts && gm && ts->B > 0 && ts->S > 0 && (gm->m == 2 || gm->m == 3) && ts->nodes && ts->root_sum &&
-         ts->leaf_parent && ts->leaf_action && ts->depth && ts->path && gm->g && gm->considered && gm->seq;
+  return tree_ok(ts) && gm && (gm->m == 2 || gm->m == 3) && gm->g && gm->considered && gm->seq;
 }
 
 }  // namespace

@@ -178,54 +178,39 @@ __global__ void ctx_advance_kernel(int32_t* ctx) {
   if (threadIdx.x < 3) ctx[threadIdx.x] += 1;  // search id, step index, episode row
 }
 
-TreeArgs make_args(void* nodes, float* root_sum, uint32_t* calls, int32_t* leaf_parent, int32_t* leaf_action,
-                   int32_t* depth, int32_t* path, const float* sqrt_tab, const float* c_tab, int B, int S,
-                   int env_offset, int search_id, uint64_t seed, const int32_t* ctx) {
-  return TreeArgs{(Node*)nodes, root_sum, calls, leaf_parent, leaf_action, depth, path, sqrt_tab, c_tab,
-                  B,            S,        env_offset, search_id, seed, ctx};
-}
-
 }  // namespace
-
-#define MZ_TREE_PARAMS                                                                                       \
-  void *nodes, float *root_sum, uint32_t *calls, int32_t *leaf_parent, int32_t *leaf_action, int32_t *depth, \
-      int32_t *path, const float *sqrt_tab, const float *c_tab, int B, int S, int env_offset, int search_id, \
-      uint64_t seed, const int32_t *ctx
-#define MZ_TREE_ARGS \
-  make_args(nodes, root_sum, calls, leaf_parent, leaf_action, depth, path, sqrt_tab, c_tab, B, S, env_offset, search_id, \
-            seed, ctx)
 
 extern "C" {
 
 int mzba_mcts_node_bytes() { return (int)sizeof(Node); }
 
-int mzba_mcts_root(MZ_TREE_PARAMS, const float* v_root, const float* pi_root, const float* noise_in,
+int mzba_mcts_root(const mzba_tree_step* ts, const float* v_root, const float* pi_root, const float* noise_in,
                    float* noise_out, float w_pol, float w_noise, const float* w_dev, float alpha, hipStream_t stream) {
-  MZ_CHECK_ARG(B > 0 && S > 0, -1);
-  hipLaunchKernelGGL(root_init_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, MZ_TREE_ARGS, v_root, pi_root,
+  MZ_CHECK_ARG(tree_ok_puct(ts) && v_root && pi_root, -1);
+  hipLaunchKernelGGL(root_init_kernel, dim3((ts->B + 255) / 256), dim3(256), 0, stream, tree_args(ts), v_root, pi_root,
                      noise_in, noise_out, w_pol, w_noise, w_dev, alpha);
   MZ_LAUNCH_CHECK();
   return 0;
 }
 
-int mzba_mcts_select(MZ_TREE_PARAMS, int sim, hipStream_t stream) {
-  MZ_CHECK_ARG(B > 0 && sim >= 1 && sim < S, -1);
-  hipLaunchKernelGGL(select_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, MZ_TREE_ARGS, sim);
+int mzba_mcts_select(const mzba_tree_step* ts, hipStream_t stream) {
+  MZ_CHECK_ARG(tree_ok_puct(ts) && ts->sim >= 1 && ts->sim < ts->S, -1);
+  hipLaunchKernelGGL(select_kernel, dim3((ts->B + 255) / 256), dim3(256), 0, stream, tree_args(ts), ts->sim);
   MZ_LAUNCH_CHECK();
   return 0;
 }
 
-int mzba_mcts_backup(MZ_TREE_PARAMS, int sim, const float* r, const float* v, const float* pi, float gamma,
-                     hipStream_t stream) {
-  MZ_CHECK_ARG(B > 0 && sim >= 0 && sim < S, -1);
-  hipLaunchKernelGGL(backup_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, MZ_TREE_ARGS, sim, r, v, pi, gamma);
+int mzba_mcts_backup(const mzba_tree_step* ts, const float* v, const float* pi, hipStream_t stream) {
+  MZ_CHECK_ARG(tree_ok_puct(ts) && ts->sim >= 0 && ts->sim < ts->S && ts->r && v && pi, -1);
+  hipLaunchKernelGGL(backup_kernel, dim3((ts->B + 255) / 256), dim3(256), 0, stream, tree_args(ts), ts->sim, ts->r, v,
+                     pi, ts->gamma);
   MZ_LAUNCH_CHECK();
   return 0;
 }
 
-int mzba_mcts_results(MZ_TREE_PARAMS, int64_t* counts, float* values, hipStream_t stream) {
-  MZ_CHECK_ARG(B > 0, -1);
-  hipLaunchKernelGGL(results_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, MZ_TREE_ARGS, counts, values);
+int mzba_mcts_results(const mzba_tree_step* ts, int64_t* counts, float* values, hipStream_t stream) {
+  MZ_CHECK_ARG(tree_ok_puct(ts) && counts && values, -1);
+  hipLaunchKernelGGL(results_kernel, dim3((ts->B + 255) / 256), dim3(256), 0, stream, tree_args(ts), counts, values);
   MZ_LAUNCH_CHECK();
   return 0;
 }

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/mzba.h"
+#include "tree_tensors.h"
 
 namespace {
 
@@ -652,16 +653,12 @@ void prediction_tree_(const RunPtr& rn, const at::Tensor& h, at::Tensor& pi, at:
   check_batch(rn, r, 1, "r");
   TORCH_CHECK(rn->fused_ok(), "mz::prediction_tree_: the tree step rides on the fused prediction launch "
                               "(bf16 nets, 256 channels, 4x5 latent, fused kernels enabled)");
-  const int64_t B = rn->B;
-  for (auto* t : {&root_sum, &calls, &leaf_parent, &leaf_action, &depth}) check_batch(rn, *t, 1, "tree buffer");
-  TORCH_CHECK(S > 0 && sim >= 0 && sim < S, "mz::prediction_tree_: sim must be in [0, S)");
-  TORCH_CHECK(nodes.numel() == B * (S + 1) * mzba_mcts_node_bytes() && path.numel() == B * (S + 1) &&
-                  sqrt_tab.numel() >= S + 1 && c_tab.numel() >= S + 1,
-              "mz::prediction_tree_: tree buffer sizes do not match B = ", B, ", S = ", S);
-  mzba_tree_step t{nodes.data_ptr(), vp<float>(root_sum), vp<uint32_t>(calls), vp<int32_t>(leaf_parent),
-                   vp<int32_t>(leaf_action), vp<int32_t>(depth), vp<int32_t>(path), vp<float>(sqrt_tab),
-                   vp<float>(c_tab), (int)B, (int)S, (int)env_offset, (int)search_id, (uint64_t)seed,
-                   vp<int32_t>(ctx), (int)sim, (float)gamma, vp<float>(r)};
+  mzba_tree_step t = tree_step_of(rn->B, nodes, root_sum, calls, leaf_parent, leaf_action, depth, path, sqrt_tab, c_tab,
+                                  S, env_offset, search_id, seed, ctx);
+  TORCH_CHECK(sim >= 0 && sim < S, "mz::prediction_tree_: sim must be in [0, S)");
+  t.sim = (int)sim;
+  t.gamma = (float)gamma;
+  t.r = vp<float>(r);
   rn->prediction(h, pi, v, c10::nullopt, c10::nullopt, &t, hs);
 }
 

@@ -15,16 +15,11 @@
 #include <vector>
 
 #include "../../include/mzba.h"
+#include "tree_tensors.h"
 
 namespace {
 
 hipStream_t cur_stream(const at::Tensor& t) { return c10::hip::getCurrentHIPStream(t.device().index()).stream(); }
-
-void check_dev(const at::Tensor& t, const char* name, at::ScalarType st) {
-  TORCH_CHECK(t.is_cuda(), "mz: ", name, " must be a device tensor");
-  TORCH_CHECK(t.scalar_type() == st, "mz: ", name, " has dtype ", t.scalar_type(), ", expected ", st);
-  TORCH_CHECK(t.is_contiguous(), "mz: ", name, " must be contiguous");
-}
 
 void check_rc(int rc, const char* fn) { TORCH_CHECK(rc == 0, "mz: ", fn, " failed with code ", rc); }
 
@@ -93,38 +88,7 @@ at::Tensor grayscale(const at::Tensor& state) {
 }
 
 // ---- search trees --------------------------------------------------------------------------------
-struct Tree {
-  void* nodes;
-  float* root_sum;
-  uint32_t* calls;
-  int32_t *leaf_parent, *leaf_action, *depth, *path;
-  const float *sqrt_tab, *c_tab;
-  int B, S;
-};
-
-Tree tree_of(at::Tensor& nodes, at::Tensor& root_sum, at::Tensor& calls, at::Tensor& leaf_parent,
-             at::Tensor& leaf_action, at::Tensor& depth, at::Tensor& path, const at::Tensor& sqrt_tab,
-             const at::Tensor& c_tab, int64_t S) {
-  check_dev(nodes, "nodes", at::kByte);
-  check_dev(root_sum, "root_sum", at::kFloat);
-  check_dev(calls, "calls", at::kInt);
-  check_dev(leaf_parent, "leaf_parent", at::kInt);
-  check_dev(leaf_action, "leaf_action", at::kInt);
-  check_dev(depth, "depth", at::kInt);
-  check_dev(path, "path", at::kInt);
-  check_dev(sqrt_tab, "sqrt_tab", at::kFloat);
-  check_dev(c_tab, "c_tab", at::kFloat);
-  const int B = (int)root_sum.numel();
-  TORCH_CHECK(S > 0 && B > 0, "mz: empty tree batch");
-  TORCH_CHECK(nodes.numel() == (int64_t)B * (S + 1) * mzba_mcts_node_bytes(), "mz: nodes must be B x (S+1) nodes");
-  TORCH_CHECK(calls.numel() == B && leaf_parent.numel() == B && leaf_action.numel() == B && depth.numel() == B &&
-                  path.numel() == (int64_t)B * (S + 1) && sqrt_tab.numel() >= S + 1 && c_tab.numel() >= S + 1,
-              "mz: tree buffer sizes do not match B = ", B, ", S = ", S);
-  return Tree{nodes.data_ptr(), root_sum.data_ptr<float>(), reinterpret_cast<uint32_t*>(calls.data_ptr<int32_t>()),
-              leaf_parent.data_ptr<int32_t>(), leaf_action.data_ptr<int32_t>(), depth.data_ptr<int32_t>(),
-              path.data_ptr<int32_t>(), sqrt_tab.data_ptr<float>(), c_tab.data_ptr<float>(), B, (int)S};
-}
-
+// the nine tree tensors + S are checked and turned into the ABI's mzba_tree_step in tree_tensors.h
 #define MZ_TREE_SCHEMA                                                                                          \
   "Tensor(a!) nodes, Tensor(b!) root_sum, Tensor(c!) calls, Tensor(d!) leaf_parent, Tensor(e!) leaf_action, " \
   "Tensor(f!) depth, Tensor(g!) path, Tensor sqrt_tab, Tensor c_tab, int S, int env_offset, int search_id, "   \
@@ -136,14 +100,12 @@ Tree tree_of(at::Tensor& nodes, at::Tensor& root_sum, at::Tensor& calls, at::Ten
   at::Tensor &nodes, at::Tensor &root_sum, at::Tensor &calls, at::Tensor &leaf_parent, at::Tensor &leaf_action, \
       at::Tensor &depth, at::Tensor &path, const at::Tensor &sqrt_tab, const at::Tensor &c_tab, int64_t S,      \
       int64_t env_offset, int64_t search_id, int64_t seed, const c10::optional<at::Tensor>&ctx
-#define MZ_TREE_ARGS(t)                                                                                           \
-  t.nodes, t.root_sum, t.calls, t.leaf_parent, t.leaf_action, t.depth, t.path, t.sqrt_tab, t.c_tab, t.B, t.S,     \
-      (int)env_offset, (int)search_id, (uint64_t)seed, ptr_or_null<int32_t>(ctx)
 
 void mcts_root_(MZ_TREE_DECL, const at::Tensor& v_root, const at::Tensor& pi_root,
                 const c10::optional<at::Tensor>& noise_in, at::Tensor& noise_out, double w_pol, double w_noise,
                 const c10::optional<at::Tensor>& w_dev, double alpha) {
-  Tree t = tree_of(nodes, root_sum, calls, leaf_parent, leaf_action, depth, path, sqrt_tab, c_tab, S);
+  const mzba_tree_step t = tree_step_of(root_sum.numel(), nodes, root_sum, calls, leaf_parent, leaf_action, depth, path,
+                                        sqrt_tab, c_tab, S, env_offset, search_id, seed, ctx);
   check_dev(v_root, "v_root", at::kFloat);
   check_dev(pi_root, "pi_root", at::kFloat);
   check_dev(noise_out, "noise_out", at::kFloat);
@@ -153,42 +115,44 @@ void mcts_root_(MZ_TREE_DECL, const at::Tensor& v_root, const at::Tensor& pi_roo
     check_dev(*noise_in, "noise_in", at::kFloat);
     TORCH_CHECK(noise_in->numel() == 3LL * t.B, "mz::mcts_root_: noise_in [B, 3]");
   }
-  check_rc(mzba_mcts_root(MZ_TREE_ARGS(t), v_root.data_ptr<float>(), pi_root.data_ptr<float>(),
-                          ptr_or_null<float>(noise_in), noise_out.data_ptr<float>(), (float)w_pol, (float)w_noise,
-                          ptr_or_null<float>(w_dev), (float)alpha, cur_stream(v_root)),
+  check_rc(mzba_mcts_root(&t, v_root.data_ptr<float>(), pi_root.data_ptr<float>(), ptr_or_null<float>(noise_in),
+                          noise_out.data_ptr<float>(), (float)w_pol, (float)w_noise, ptr_or_null<float>(w_dev),
+                          (float)alpha, cur_stream(v_root)),
            "mzba_mcts_root");
 }
 
 void mcts_select_(MZ_TREE_DECL, int64_t sim) {
-  Tree t = tree_of(nodes, root_sum, calls, leaf_parent, leaf_action, depth, path, sqrt_tab, c_tab, S);
-  check_rc(mzba_mcts_select(MZ_TREE_ARGS(t), (int)sim, cur_stream(root_sum)), "mzba_mcts_select");
+  mzba_tree_step t = tree_step_of(root_sum.numel(), nodes, root_sum, calls, leaf_parent, leaf_action, depth, path,
+                                  sqrt_tab, c_tab, S, env_offset, search_id, seed, ctx);
+  t.sim = (int)sim;
+  check_rc(mzba_mcts_select(&t, cur_stream(root_sum)), "mzba_mcts_select");
 }
 
 void mcts_backup_(MZ_TREE_DECL, int64_t sim, const at::Tensor& r, const at::Tensor& v, const at::Tensor& pi,
                   double gamma) {
-  Tree t = tree_of(nodes, root_sum, calls, leaf_parent, leaf_action, depth, path, sqrt_tab, c_tab, S);
+  mzba_tree_step t = tree_step_of(root_sum.numel(), nodes, root_sum, calls, leaf_parent, leaf_action, depth, path,
+                                  sqrt_tab, c_tab, S, env_offset, search_id, seed, ctx);
   check_dev(r, "r", at::kFloat);
   check_dev(v, "v", at::kFloat);
   check_dev(pi, "pi", at::kFloat);
   TORCH_CHECK(r.numel() == t.B && v.numel() == t.B && pi.numel() == 3LL * t.B, "mz::mcts_backup_: r, v [B], pi [B, 3]");
-  check_rc(mzba_mcts_backup(MZ_TREE_ARGS(t), (int)sim, r.data_ptr<float>(), v.data_ptr<float>(), pi.data_ptr<float>(),
-                            (float)gamma, cur_stream(r)),
-           "mzba_mcts_backup");
+  t.sim = (int)sim;
+  t.gamma = (float)gamma;
+  t.r = r.data_ptr<float>();
+  check_rc(mzba_mcts_backup(&t, v.data_ptr<float>(), pi.data_ptr<float>(), cur_stream(r)), "mzba_mcts_backup");
 }
 
-void mcts_results_(const at::Tensor& nodes_, const at::Tensor& root_sum_, const at::Tensor& calls_,
-                   const at::Tensor& leaf_parent_, const at::Tensor& leaf_action_, const at::Tensor& depth_,
-                   const at::Tensor& path_, const at::Tensor& sqrt_tab, const at::Tensor& c_tab, int64_t S,
+void mcts_results_(const at::Tensor& nodes, const at::Tensor& root_sum, const at::Tensor& calls,
+                   const at::Tensor& leaf_parent, const at::Tensor& leaf_action, const at::Tensor& depth,
+                   const at::Tensor& path, const at::Tensor& sqrt_tab, const at::Tensor& c_tab, int64_t S,
                    int64_t env_offset, int64_t search_id, int64_t seed, const c10::optional<at::Tensor>& ctx,
                    at::Tensor& values, at::Tensor& counts) {
-  at::Tensor nodes = nodes_, root_sum = root_sum_, calls = calls_, leaf_parent = leaf_parent_,
-             leaf_action = leaf_action_, depth = depth_, path = path_;  // read only: handles, not copies
-  Tree t = tree_of(nodes, root_sum, calls, leaf_parent, leaf_action, depth, path, sqrt_tab, c_tab, S);
+  const mzba_tree_step t = tree_step_of(root_sum.numel(), nodes, root_sum, calls, leaf_parent, leaf_action, depth, path,
+                                        sqrt_tab, c_tab, S, env_offset, search_id, seed, ctx);
   check_dev(values, "values", at::kFloat);
   check_dev(counts, "counts", at::kLong);
   TORCH_CHECK(values.numel() == t.B && counts.numel() == 3LL * t.B, "mz::mcts_results_: values [B], counts [B, 3]");
-  check_rc(mzba_mcts_results(MZ_TREE_ARGS(t), counts.data_ptr<int64_t>(), values.data_ptr<float>(),
-                             cur_stream(root_sum)),
+  check_rc(mzba_mcts_results(&t, counts.data_ptr<int64_t>(), values.data_ptr<float>(), cur_stream(root_sum)),
            "mzba_mcts_results");
 }
 

@@ -1203,9 +1203,8 @@ int mzba_tower_fused(const void* in, long long in_env_stride, const int32_t* slo
               nblocks, B, x, TreeArgs{}, 0, 0, 0.f, nullptr};
   if (x.tree) {
     const mzba_tree_step& t = *x.tree;
-    MZ_CHECK_ARG(x.epilogue == 2 && t.B == B && t.sim >= 0 && t.sim < t.S && t.r && t.nodes, -3);
-    a.tree = TreeArgs{(Node*)t.nodes, t.root_sum, t.calls, t.leaf_parent, t.leaf_action, t.depth, t.path,
-                      t.sqrt_tab, t.c_tab, t.B, t.S, t.env_offset, t.search_id, t.seed, t.ctx};
+    MZ_CHECK_ARG(x.epilogue == 2 && tree_ok_puct(&t) && t.B == B && t.sim >= 0 && t.sim < t.S && t.r, -3);
+    a.tree = tree_args(&t);
     a.tree_on = 1;
     a.tree_sim = t.sim;
     a.tree_gamma = t.gamma;

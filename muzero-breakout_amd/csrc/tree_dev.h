@@ -32,6 +32,21 @@ struct TreeArgs {
   const int32_t* ctx;   // optional device step context (graph replay): ctx[0] = search id
 };
 
+// host: the ABI's tree (include/mzba.h mzba_tree_step) as the kernels' argument
+inline TreeArgs tree_args(const mzba_tree_step* ts) {
+  return TreeArgs{(Node*)ts->nodes, ts->root_sum, ts->calls, ts->leaf_parent, ts->leaf_action, ts->depth, ts->path,
+                  ts->sqrt_tab, ts->c_tab, ts->B, ts->S, ts->env_offset, ts->search_id, ts->seed, ts->ctx};
+}
+
+// host: a tree every tree kernel may run on; the PUCT kernels (ucb_select) also read calls and the two tables
+inline bool tree_ok(const mzba_tree_step* ts) {
+  return ts && ts->B > 0 && ts->S > 0 && ts->nodes && ts->root_sum && ts->leaf_parent && ts->leaf_action &&
+         ts->depth && ts->path;
+}
+inline bool tree_ok_puct(const mzba_tree_step* ts) {
+  return tree_ok(ts) && ts->calls && ts->sqrt_tab && ts->c_tab;
+}
+
 MZ_DEV int tree_search_id(const TreeArgs& t) { return t.ctx ? t.ctx[0] : t.search_id; }
 
 // ucb_action (mcts.py:45-71) on one node. k: this env's ucb_action call counter (the tie-break

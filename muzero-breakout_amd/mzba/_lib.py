@@ -86,11 +86,12 @@ SIGNATURES = {
     "mzba_heads_set_variant": [I],
     "mzba_heads_bf16": [I, P, P, P, I, I, I, P, P, P, P, P, I, I, I, P, P, F, F, I, P],
     "mzba_mcts_node_bytes": [],
-    "mzba_mcts_root": [P, P, P, P, P, P, P, P, P, I, I, I, I, U64, P, P, P, P, P, F, F, P, F, P],
-    "mzba_mcts_select": [P, P, P, P, P, P, P, P, P, I, I, I, I, U64, P, I, P],
-    "mzba_mcts_backup": [P, P, P, P, P, P, P, P, P, I, I, I, I, U64, P, I, P, P, P, F, P],
-    "mzba_mcts_results": [P, P, P, P, P, P, P, P, P, I, I, I, I, U64, P, P, P, P],
-    # Gumbel search (gumbel.hip): the tree as a TreeStep, the mode's state as a Gumbel, both by reference
+    # the trees as a TreeStep by reference (PUCT: mcts.hip)
+    "mzba_mcts_root": [P, P, P, P, P, F, F, P, F, P],
+    "mzba_mcts_select": [P, P],
+    "mzba_mcts_backup": [P, P, P, P],
+    "mzba_mcts_results": [P, P, P, P],
+    # Gumbel search (gumbel.hip): the same TreeStep and the mode's state as a Gumbel
     "mzba_gumbel_root": [P, P, P, P, P, P, P],
     "mzba_gumbel_step": [P, P, P, P, P],
     "mzba_gumbel_results": [P, P, P, P, P, P, P],
@@ -161,7 +162,7 @@ _lib = None
 
 
 class TreeStep(ctypes.Structure):
-    """include/mzba.h mzba_tree_step (backup + next select inside the fused prediction step)."""
+    """include/mzba.h mzba_tree_step (a batch of search trees and one step's values; TreeState.step fills it)."""
     _fields_ = [("nodes", P), ("root_sum", P), ("calls", P), ("leaf_parent", P), ("leaf_action", P), ("depth", P),
                 ("path", P), ("sqrt_tab", P), ("c_tab", P), ("B", I), ("S", I), ("env_offset", I),
                 ("search_id", I), ("seed", U64), ("ctx", P), ("sim", I), ("gamma", F), ("r", P)]
@@ -273,6 +274,17 @@ def require_gpu():
 
 def stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def capture(body):
+    """body()'s launches captured on a side stream into a HIP graph, which is returned."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        body()
+    torch.cuda.current_stream().wait_stream(s)
+    return g
 
 
 def ptr(t):

@@ -82,12 +82,10 @@ class ActingLoop:
         # explicit (argument, else cfg["pow_threads"], else 1 — what the oracle assumes), never inferred
         self.pow_threads = int(cfg.get("pow_threads", 1) if pow_threads is None else pow_threads)
         dev = agent.device
-        # graph-replayable schedule values (train_torch.py:129-135): 1/T in double for the sampling
-        # kernel, (f32(1 - noise_weight), f32(noise_weight)) for the root expansion
+        # graph-replayable schedule value (train_torch.py:129-132): 1/T in double for the sampling kernel (the
+        # root's noise weight is the search workspace's, SearchWorkspace.sync_noise_weight)
         self.inv_t_dev = torch.ones(1, dtype=torch.float64, device=dev)
-        self.root_w_dev = torch.zeros(2, dtype=torch.float32, device=dev)
         self._temperature = None
-        self._noise_weight = None
         self.temperature = temperature
         mcfg = cfg["model"]
         self.Lh = mcfg["state_history_length"]
@@ -145,10 +143,7 @@ class ActingLoop:
             self.inv_t_dev.fill_(1.0 / t)  # Python's `1/self.temperature` (double), train_torch.py:192
 
     def _sync_noise_weight(self):
-        w = self.search.noise_weight  # train_torch.py:134-135 sets it on the search object
-        if w != self._noise_weight:
-            self._noise_weight = w
-            self.root_w_dev.copy_(torch.tensor([np.float32(1 - w), np.float32(w)], dtype=torch.float32))
+        self.ws.sync_noise_weight()  # the buffer and its sync are the search workspace's
 
     def reset(self, episode=None, params=None):
         """_acting_stage :166-167: env.reset + _pad_initial_state."""
@@ -169,10 +164,8 @@ class ActingLoop:
         # _prepare_mcts_input + create_hidden_state_root -> pool slot 0
         env.build_rep_input(self.rep_in, self.cs, self.agent.dtype == "bf16")
         self.rep_runner.representation(self.rep_in, ws.cur, pool=ws.pool, pool_env_stride=(ws.S + 1) * n)
-        if self.gumbel:
-            values, counts, _ = ws.run_gumbel(self.search_id, self._noise_in, ctx=self.ctx)
-        else:
-            values, counts = ws.run(self.search_id, self._noise_in, ctx=self.ctx, w_dev=self.root_w_dev)
+        values, counts = ws.search(self.search_id, self._noise_in, ctx=self.ctx)
+        if not self.gumbel:
             self._sample(counts)
         L.call("mzba_record_results", L.ptr(counts), L.ptr(values),
                ctypes.byref(L.sink(self.rec, self.max_steps, self.H * self.W)), 0, L.ptr(self.ctx), L.stream())
@@ -194,13 +187,7 @@ class ActingLoop:
             raise RuntimeError("capture(): injected noise is host data per step; clear inject_noise first")
         self._noise_in = None
         self._sync_noise_weight()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=s):
-            self._act_body()
-        torch.cuda.current_stream().wait_stream(s)
-        self.graph = g
+        self.graph = L.capture(self._act_body)
 
     def act(self, eager=False):
         """One acting step t (no host synchronisation)."""

@@ -16,7 +16,6 @@ masks and frames are never written. Streamed sinks (several episodes per env) ar
 """
 import ctypes
 
-import numpy as np
 import torch
 
 from . import _lib as L
@@ -41,10 +40,6 @@ class Reanalyser:
         self.cs = (2 * self.Lh + 63) // 64 * 64
         self.rep_in = torch.empty(B * height * width * self.cs, dtype=p.tdt, device=dev)
         self.rep_runner = agent.runner(B, height, width)
-        self.gumbel = self.search.kind == "gumbel"
-        # (f32(1 - noise_weight), f32(noise_weight)) of the root expansion, read on the device
-        self.root_w_dev = torch.zeros(2, dtype=torch.float32, device=dev)
-        self._noise_weight = None
         # device step context [search id, 0, sink row t]: the one captured row graph reads both from here
         self.ctx = torch.zeros(3, dtype=torch.int32, device=dev)
         self.graph = None
@@ -55,12 +50,6 @@ class Reanalyser:
         """Clones of the sink's first T rows and of g(s0): an archive to reanalyse while the stage goes on
         recording into its own sink."""
         return ({k: (None if v is None else v[:T].clone()) for k, v in rec.items()}, frame0.clone())
-
-    def _set_noise_weight(self, w):
-        w = self.search.noise_weight if w is None else w
-        if w != self._noise_weight:
-            self._noise_weight = w
-            self.root_w_dev.copy_(torch.tensor([np.float32(1 - w), np.float32(w)], dtype=torch.float32))
 
     def _check(self, rec, frame0, T):
         if rec.get("start") is not None:
@@ -80,10 +69,7 @@ class Reanalyser:
         L.call("mzba_sink_rep_input", sk, L.ptr(frame0), self.Lh, self.pad_action, 0, L.ptr(self.ctx),
                L.ptr(self.rep_in), 1 if self.agent.dtype == "bf16" else 0, self.cs, L.stream())
         self.rep_runner.representation(self.rep_in, ws.cur, pool=ws.pool, pool_env_stride=(ws.S + 1) * ws.n)
-        if self.gumbel:
-            values, counts, _ = ws.run_gumbel(0, None, ctx=self.ctx)
-        else:
-            values, counts = ws.run(0, None, ctx=self.ctx, w_dev=self.root_w_dev)
+        values, counts = ws.search(0, ctx=self.ctx)
         L.call("mzba_record_results_masked", L.ptr(counts), L.ptr(values), sk, 0, L.ptr(self.ctx), L.stream())
 
     def refresh(self, rec, frame0, T, search_id0, rows=None, noise_weight=None, use_graph=True):
@@ -113,7 +99,7 @@ class _Run:
         self.rean, self.frame0, self.n, self.use_graph = rean, frame0, len(rows), use_graph
         if not rows:
             return
-        rean._set_noise_weight(noise_weight)
+        rean.ws.sync_noise_weight(noise_weight)
         self.sink = L.sink(rec, T, rean.H * rean.W)  # held: the launches read it through this reference
         self.sk = ctypes.byref(self.sink)
         self.table = torch.tensor([[search_id0 + t, 0, t] for t in rows], dtype=torch.int32).to(rean.agent.device)
@@ -124,13 +110,7 @@ class _Run:
             if rean._graph_key != key:
                 rean.ctx.copy_(self.table[0])
                 rean._row_body(self.sk, frame0)  # eager once: lazy allocations happen outside the capture
-                s = torch.cuda.Stream()
-                s.wait_stream(torch.cuda.current_stream())
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=s):
-                    rean._row_body(self.sk, frame0)
-                torch.cuda.current_stream().wait_stream(s)
-                rean.graph, rean._graph_key = g, key
+                rean.graph, rean._graph_key = L.capture(lambda: rean._row_body(self.sk, frame0)), key
 
     def row(self, i):
         rean = self.rean

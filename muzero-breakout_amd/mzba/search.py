@@ -79,11 +79,7 @@ class GumbelState:
         self.root_n = torch.empty(B, 3, dtype=torch.int32, device=device)
 
     def _structs(self, ta, sim=0, gamma=0.0, r=None):
-        t = self.tree
-        env_offset, search_id, seed, ctx = ta
-        ts = L.TreeStep(L.addr(t.nodes), L.addr(t.root_sum), L.addr(t.calls), L.addr(t.leaf_parent),
-                        L.addr(t.leaf_action), L.addr(t.depth), L.addr(t.path), L.addr(t.sqrt_tab), L.addr(t.c_tab),
-                        t.B, t.S, env_offset, search_id, seed, L.addr(ctx), sim, gamma, L.addr(r))
+        ts = self.tree.step(*ta, sim, gamma, r)
         gm = L.Gumbel(L.addr(self.g), L.addr(self.considered), L.addr(self.seq), self.m, self.c_visit, self.c_scale,
                       self.scale)
         return ctypes.byref(ts), ctypes.byref(gm)
@@ -124,6 +120,13 @@ class TreeState:
         int32[3] step context (its [0] overrides search_id; graph replay)."""
         return (self.nodes, self.root_sum, self.calls, self.leaf_parent, self.leaf_action, self.depth, self.path,
                 self.sqrt_tab, self.c_tab, self.S, env_offset, search_id, seed, ctx)
+
+    def step(self, env_offset, search_id, seed, ctx=None, sim=0, gamma=0.0, r=None):
+        """The trees as the C ABI's mzba_tree_step, for simulation `sim` where the entry point reads one."""
+        a = L.addr
+        return L.TreeStep(a(self.nodes), a(self.root_sum), a(self.calls), a(self.leaf_parent), a(self.leaf_action),
+                          a(self.depth), a(self.path), a(self.sqrt_tab), a(self.c_tab), self.B, self.S, env_offset,
+                          search_id, seed, a(ctx), sim, gamma, a(r))
 
     # individual kernels, dispatched as torch custom ops -----------------------------------------
     def root(self, tree_args, v_root, pi_root, noise_in, w_pol, w_noise, alpha, w_dev=None):
@@ -215,6 +218,10 @@ class SearchWorkspace:
         self.pi = torch.empty(B, 3, dtype=torch.float32, device=dev)
         self.runner = agent.runner(B, p.lh * 4, p.lw * 4)
         self.gumbel = GumbelState(self.tree, *search.gumbel, dev) if search.gumbel is not None else None
+        # (f32(1 - noise_weight), f32(noise_weight)) of the root expansion, read on the device: the schedule
+        # (train_torch.py:134-135) needs no new graph capture
+        self.root_w_dev = torch.zeros(2, dtype=torch.float32, device=dev)
+        self._noise_weight = None
         # backup + next select ride on the fused prediction launch (MZBA_TREE_FUSION=0: separate kernels)
         self.use_tree_fusion = os.environ.get("MZBA_TREE_FUSION", "1") != "0"
         # fused steps: latents straight from / to their node-pool slots (MZBA_POOL_SLOTS=0: through `cur`,
@@ -230,6 +237,29 @@ class SearchWorkspace:
 
     def root_slot(self):
         return self.pool.view(self.B, self.S + 1, self.n)[:, 0]
+
+    def sync_noise_weight(self, w=None):
+        """Bring root_w_dev up to `w`, by default the search object's noise_weight (train_torch.py:134-135 sets it
+        there)."""
+        w = self.s.noise_weight if w is None else w
+        if w != self._noise_weight:
+            self._noise_weight = w
+            self.root_w_dev.copy_(torch.tensor([np.float32(1 - w), np.float32(w)], dtype=torch.float32))
+
+    def search(self, search_id, noise=None, ctx=None):
+        """The configured search of the acting and reanalyse loops -> (values, counts): run_gumbel, or run with the
+        root weights of root_w_dev (sync_noise_weight)."""
+        if self.s.kind == "gumbel":
+            return self.run_gumbel(search_id, noise, ctx=ctx)[:2]
+        return self.run(search_id, noise, ctx=ctx, w_dev=self.root_w_dev)
+
+    def _dynamics(self, sim, direct):
+        """Simulation sim's dynamics step: parent latents gathered from the node pool, the new latent to slot
+        sim + 1 (and to `cur` unless `direct`), decoded rewards to r."""
+        env_stride = (self.S + 1) * self.n
+        self.runner.dynamics(self.pool, self.tree.leaf_action, None if direct else self.cur, self.r,
+                             slot=self.tree.leaf_parent, env_stride=env_stride, slot_stride=self.n, pool=self.pool,
+                             pool_env_stride=env_stride, pool_slot=sim + 1)
 
     def run(self, search_id, noise=None, ctx=None, w_dev=None):
         """mcts.py:24-71 on the device. Root latent must be in pool slot 0. With `ctx` the
@@ -249,13 +279,10 @@ class SearchWorkspace:
         w_noise = float(np.float32(s.noise_weight))
         self.tree.root(ta, self.v, self.pi, noise, w_pol, w_noise, s.dirchlet_alpha, w_dev)
         gamma = float(np.float32(s.discount))
-        env_stride = (S + 1) * n
         for sim in range(S):
             if sim > 0 and not fused:
                 self.tree.select(ta, sim)
-            rn.dynamics(self.pool, self.tree.leaf_action, None if direct else self.cur, self.r,
-                        slot=self.tree.leaf_parent, env_stride=env_stride, slot_stride=n, pool=self.pool,
-                        pool_env_stride=env_stride, pool_slot=sim + 1)
+            self._dynamics(sim, direct)
             if fused:  # prediction + backup(sim) + select(sim + 1) in one launch
                 rn.prediction(slots[:, sim + 1] if direct else self.cur, self.pi, self.v, tree=(ta, sim, gamma, self.r))
             else:
@@ -284,11 +311,8 @@ class SearchWorkspace:
             record.update(v_root=self.v.clone(), pi_root=self.pi.clone(), r=[], v=[], pi=[])
         gs.root(ta, self.v, self.pi, g)
         gamma = float(np.float32(s.discount))
-        env_stride = (S + 1) * n
         for sim in range(S):
-            rn.dynamics(self.pool, self.tree.leaf_action, None if direct else self.cur, self.r,
-                        slot=self.tree.leaf_parent, env_stride=env_stride, slot_stride=n, pool=self.pool,
-                        pool_env_stride=env_stride, pool_slot=sim + 1)
+            self._dynamics(sim, direct)
             rn.prediction(slots[:, sim + 1] if direct else self.cur, self.pi, self.v)
             if record is not None:
                 for k, t in (("r", self.r), ("v", self.v), ("pi", self.pi)):

@@ -119,6 +119,33 @@ def test_env_and_replay_entry_points_reject_bad_arguments_without_gpu():
     assert plan(-1) == -2
 
 
+def test_tree_entry_points_reject_bad_arguments_without_gpu():
+    """The four PUCT entry points check their mzba_tree_step before any HIP call: a NULL struct, B = 0, S = 0 and a
+    NULL nodes return -1, and so do a simulation outside the entry point's range and a backup without rewards."""
+    from ctypes import byref, c_void_p
+    from mzba import _lib
+    L = _lib.lib()
+    a = 4096
+    p = c_void_p(a)
+
+    def ts(B=3, S=4, sim=1, nodes=a, r=a):
+        return byref(_lib.TreeStep(nodes, *[a] * 8, B, S, 0, 0, 1, None, sim, 0.985, r))
+
+    calls = {
+        "mzba_mcts_root": lambda t: (t, p, p, None, p, 0.825, 0.175, None, 0.25, None),
+        "mzba_mcts_select": lambda t: (t, None),
+        "mzba_mcts_backup": lambda t: (t, p, p, None),
+        "mzba_mcts_results": lambda t: (t, p, p, None),
+    }
+    for name, args in calls.items():
+        for t in (None, ts(B=0), ts(S=0), ts(nodes=None)):
+            assert getattr(L, name)(*args(t)) == -1, name
+    assert L.mzba_mcts_select(ts(sim=0), None) == -1
+    assert L.mzba_mcts_select(ts(sim=4), None) == -1
+    assert L.mzba_mcts_backup(ts(sim=4), p, p, None) == -1
+    assert L.mzba_mcts_backup(ts(r=None), p, p, None) == -1
+
+
 def test_node_layout_is_one_line():
     from mzba import _lib
     assert _lib.lib().mzba_mcts_node_bytes() == 64
