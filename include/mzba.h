@@ -606,6 +606,25 @@ int mzba_ctx_advance(int32_t* ctx, hipStream_t stream);
 int mzba_sink_rep_input(const mzba_sink* sink, const uint8_t* frame0, int L, int pad_action, int t,
                         const int32_t* ctx, void* out, int out_bf16, int Cs, hipStream_t stream);
 
+/* mzba_sink_rep_input for a streamed sink (sink->start, mzba_env_restart_compact): same output, same
+ * row convention. The history of env b at row t stops at its segment's start: with t0 = the greatest row r <= t with
+ * start[r][b] != 0 and s0 the state packed in that word, F = (L - 1) x g(s0) followed by the frames of rows
+ * t0 .. t - 1 and A = L x pad_action followed by the actions of rows t0 .. t - 1; the channels are those of
+ * mzba_sink_rep_input (channel L - 1 is g(s0) when t = t0). g(s0) is rendered from the word (H, W, paddle_width,
+ * brick_rows as in the env), so there is no frame0: row 0 of a streamed sink carries a word for every env.
+ * mzba_sink_origin fills origin i32 [T][B] = t0(t, b) (0 where no word precedes), once per sink: one thread per env
+ *   walks its column. Reads sink->start. -1: a NULL sink, start or origin, T or B <= 0.
+ * mzba_sink_rep_input_stream reads origin[t][b] and the start word at that row in place of a search through the start
+ *   words. Reads sink->action and sink->frame (rows in [t0, t)), never outside the first sink->T rows whatever origin
+ *   and the words hold (t0 is clamped to [0, t]); on a sink without a word at row 0 the output is finite and otherwise
+ *   unspecified. -1: what mzba_sink_rep_input refuses (frame0 apart), a NULL sink->start or origin, H * W != sink->HW,
+ *   H or W outside [1, 256], paddle_width outside [1, W], brick_rows outside [1, H]. A device row outside
+ *   [0, sink->T) reads and writes nothing. */
+int mzba_sink_origin(const mzba_sink* sink, int32_t* origin, hipStream_t stream);
+int mzba_sink_rep_input_stream(const mzba_sink* sink, const int32_t* origin, int H, int W, int paddle_width,
+                               int brick_rows, int L, int pad_action, int t, const int32_t* ctx, void* out, int out_bf16,
+                               int Cs, hipStream_t stream);
+
 /* mzba_record_results for the envs with rec->mask[t][b] != 0 only: the other envs' counts and values at row t keep
  * what the acting loop left there. -1: t outside [0, rec->T) (without ctx), a NULL mask, counts or values. */
 int mzba_record_results_masked(const int64_t* counts, const float* values, const mzba_sink* rec, int t,
@@ -619,6 +638,13 @@ int mzba_record_results_masked(const int64_t* counts, const float* values, const
 int mzba_replay_rewrite(const mzba_sink* sink, const uint8_t* frame0, const int32_t* lens, const float* rsum,
                         const int32_t* offsets, int n_windows, int j_first, const mzba_replay_ring* ring, int head,
                         const float* dpow, hipStream_t stream);
+
+/* The same for mzba_replay_stream_write (same table, nmax, n_segments, n_windows, head): its windows j in
+ * [max(j_first, n_windows - cap), n_windows) again through the segment table, writing ONLY counts, values and
+ * targets of ring slot (head + j) % cap. Reads the sink's reward, counts and values; no frame is rendered. */
+int mzba_replay_stream_rewrite(const mzba_sink* sink, const int32_t* table, int nmax, int n_segments, int n_windows,
+                               int j_first, const mzba_replay_ring* ring, int head, const float* dpow,
+                               hipStream_t stream);
 
 /* ===================== learner: one minibatch of RLSystem._training_stage
  * (train_torch.py:380-407) — _k_step_rollout (:487-528) with train-mode BN, loss_fn (:33-66),

@@ -11,6 +11,11 @@
 //   channels 2L .. Cs-1 : zero
 //   sink_rep_input_kernel    the gather: NHWC [B][HW][Cs] f32 / bf16, the layout of mzba_build_rep_input;
 //   record_masked_kernel     mzba_record_results for the envs recorded at row t only.
+// A streamed sink holds several episodes per env, and the restart kernel refills the ring with pad
+// actions and g(s0), so the history of env b at row t stops at t0 = the greatest row <= t with a start word: the same
+// F and A with "rows t0 .. t - 1" and the g(s0) of that word; a source row r comes from the sink iff r >= t0. The
+// kernel's Older parameter says where the older ones come from (FromFrame0: row 0 and a stored g(s0); FromOrigin: t0
+// from a (T, B) origin table filled once per sink, sink_origin_kernel, and g(s0) rendered from the word at that row).
 #include "common.h"
 
 namespace {
@@ -65,15 +70,28 @@ MZ_DEV int img_at(int px, int c, int S) { return px * S + (px >> 4) * 8 + c; }
 // i / d for i d < 2^32 with inv = 0xffffffff / d + 1 (d >= 2; d == 1 has no such inv)
 MZ_DEV int div_by(int i, int d, uint32_t inv) { return d == 1 ? i : (int)__umulhi((uint32_t)i, inv); }
 
-// One workgroup = one run of up to RUN pixels of env b. Phase 1: the L source rows' runs, 16 B per lane, scattered
-// into an LDS image [pixel][channel] of gray codes; the Cs - L channels that do not depend on the pixel (action planes,
-// zero padding) once, in the output's element type. Phase 2, 16-B chunks of the NHWC output: first the FC chunks per
-// pixel that hold frame channels (a lane reads its chunk's codes with one LDS read, 8 channels of one pixel in bf16, 4
-// in f32, and converts them), then the Cs / EPT - FC chunks per pixel that are the plane values as they stand. Whole
-// waves take one kind or the other, and consecutive lanes store consecutive chunks of a pixel.
-template <typename T>
+// where a source row older than the env's episode comes from
+struct FromFrame0 {  // a lockstep sink: the episode starts at row 0, its g(s0) is stored as u8 [B][HW]
+  static constexpr bool streamed = false;
+  const uint8_t* frame0;
+};
+struct FromOrigin {  // a streamed sink: the episode starts at row origin[t][b] (sink_origin_kernel), whose start word
+  static constexpr bool streamed = true;  // (u32 [T][B]) renders g(s0)
+  const uint32_t* start;
+  const int32_t* origin;
+  int H, W, pw, brick_rows;
+};
+
+// One workgroup = one run of up to RUN pixels of env b. Streamed sinks only: t0 and its start word, one word each, the
+// same for the whole workgroup. Phase 1: the L source rows' runs, 16 B per lane (rendered from the start word for a
+// row < t0), scattered into an LDS image [pixel][channel] of gray codes; the Cs - L channels that do not depend on the
+// pixel (action planes, zero padding) once, in the output's element type. Phase 2, 16-B chunks of the NHWC output:
+// first the FC chunks per pixel that hold frame channels (a lane reads its chunk's codes with one LDS read, 8 channels
+// of one pixel in bf16, 4 in f32, and converts them), then the Cs / EPT - FC chunks per pixel that are the plane values
+// as they stand. Whole waves take one kind or the other, and consecutive lanes store consecutive chunks of a pixel.
+template <typename T, typename Older>
 __global__ __launch_bounds__(256) void sink_rep_input_kernel(
-    const uint8_t* __restrict__ action, const uint8_t* __restrict__ frame, const uint8_t* __restrict__ frame0,
+    const uint8_t* __restrict__ action, const uint8_t* __restrict__ frame, const Older older,
     T* __restrict__ out, int rows, int B, int HW, int L, int S, int pad_action, int t_arg,
     const int32_t* __restrict__ ctx, int Cs, int runs, uint32_t inv_fc, uint32_t inv_pc) {
   constexpr int EPT = 16 / (int)sizeof(T);  // elements of a 16-B chunk
@@ -85,11 +103,16 @@ __global__ __launch_bounds__(256) void sink_rep_input_kernel(
   const int npix = min(RUN, HW - p0), nch = npix >> 4;
   T* const plane = reinterpret_cast<T*>(lds);                       // [Cs], channels < L unused (zero)
   uint8_t* const img = lds + (size_t)Cs * sizeof(T);                // Cs % 8 == 0: 16-B aligned
+  int t0 = 0, paddle = 0, bx = 0, by = 0;  // source rows < t0 are pad actions and g(s0)
+  if constexpr (Older::streamed) {  // two uniform loads, no LDS and no barrier
+    t0 = min(max(older.origin[(size_t)t * B + b], 0), t);  // whatever the table holds, a row of the sink
+    mz_start_unpack(older.start[(size_t)t0 * B + b], paddle, bx, by);
+  }
   for (int c = tid; c < Cs; c += 256) {
     float v = 0.f;
     if (c >= L && c < 2 * L) {
       const int r = t + c - 2 * L;
-      const int a = r < 0 ? pad_action : (int)action[(size_t)r * B + b];
+      const int a = r < t0 ? pad_action : (int)action[(size_t)r * B + b];
       v = (float)a / 3.0f;
     }
     st(plane + c, v);
@@ -98,8 +121,14 @@ __global__ __launch_bounds__(256) void sink_rep_input_kernel(
   for (int i = tid; i < L * nch; i += 256) {
     const int c = div_by(i, nch, inv_nch), q = i - c * nch;
     const int r = c < L - 1 ? t + c - (L - 1) : t - 1;  // r <= t - 1 < rows
-    const uint8_t* src = r < 0 ? frame0 + (size_t)b * HW : frame + ((size_t)r * B + b) * HW;
-    const uint4 v = *reinterpret_cast<const uint4*>(src + p0 + q * 16);
+    uint4 v;
+    if constexpr (Older::streamed) {
+      v = r < t0 ? mz_s0_chunk(p0 + q * 16, older.H, older.W, older.pw, older.brick_rows, paddle, bx, by)
+                 : *reinterpret_cast<const uint4*>(frame + ((size_t)r * B + b) * HW + p0 + q * 16);
+    } else {
+      const uint8_t* src = r < 0 ? older.frame0 + (size_t)b * HW : frame + ((size_t)r * B + b) * HW;
+      v = *reinterpret_cast<const uint4*>(src + p0 + q * 16);
+    }
     const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
     for (int k = 0; k < 16; ++k) img[img_at(q * 16 + k, c, S)] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
@@ -128,6 +157,19 @@ __global__ __launch_bounds__(256) void sink_rep_input_kernel(
   }
 }
 
+// origin[t][b] = the greatest row r <= t with a start word of env b (0 when there is none); one thread per
+// env walks its column, lanes of a wave read consecutive envs of a row
+__global__ __launch_bounds__(256) void sink_origin_kernel(const uint32_t* __restrict__ start, int32_t* __restrict__ origin,
+                                                          int rows, int B) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  int t0 = 0;
+  for (int t = 0; t < rows; ++t) {
+    if (start[(size_t)t * B + b]) t0 = t;
+    origin[(size_t)t * B + b] = t0;
+  }
+}
+
 // record_results_kernel (mcts.hip) for the envs recorded at row t; the other rows keep what the acting loop left
 __global__ void record_masked_kernel(const int64_t* __restrict__ counts, const float* __restrict__ values,
                                      const uint8_t* __restrict__ mask, int64_t* __restrict__ rec_counts,
@@ -145,32 +187,56 @@ __global__ void record_masked_kernel(const int64_t* __restrict__ counts, const f
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// the checks and the launch both gathers share
+template <typename Older>
+int launch_sink_rep_input(const mzba_sink& sink, Older older, int L, int pad_action, int t, const int32_t* ctx, void* out,
+                          int out_bf16, int Cs, hipStream_t stream) {
+  MZ_CHECK_ARG(sink.T > 0 && sink.B > 0 && sink.HW > 0 && sink.HW % 16 == 0 && sink.action && sink.frame && out, -1);
+  MZ_CHECK_ARG(L >= 2 && Cs >= 2 * L && Cs % 8 == 0 && pad_action >= 0 && pad_action < 3, -1);
+  MZ_CHECK_ARG(ctx || (t >= 0 && t < sink.T), -1);
+  MZ_CHECK_ARG(aligned16(sink.frame) && aligned16(out), -1);  // 16-B loads and stores
+  const int S = (L + 7) / 8 * 8;
+  const size_t lds = (size_t)Cs * (out_bf16 ? 2 : 4) + (size_t)RUN * S + RUN / 16 * 8;
+  const int runs = (sink.HW + RUN - 1) / RUN;
+  const int ept = out_bf16 ? 8 : 4, FC = (L + ept - 1) / ept, PC = Cs / ept - FC;  // div_by's reciprocals
+  const uint32_t inv_fc = FC > 1 ? 0xffffffffu / (uint32_t)FC + 1u : 0u, inv_pc = PC > 1 ? 0xffffffffu / (uint32_t)PC + 1u : 0u;
+  MZ_CHECK_ARG(lds <= 64 * 1024 && (long long)sink.B * runs < (1LL << 31), -1);
+  const dim3 grid((unsigned)(sink.B * runs));
+  if (out_bf16)
+    hipLaunchKernelGGL((sink_rep_input_kernel<bf16_t, Older>), grid, dim3(256), lds, stream, sink.action, sink.frame,
+                       older, (bf16_t*)out, sink.T, sink.B, sink.HW, L, S, pad_action, t, ctx, Cs, runs, inv_fc, inv_pc);
+  else
+    hipLaunchKernelGGL((sink_rep_input_kernel<float, Older>), grid, dim3(256), lds, stream, sink.action, sink.frame,
+                       older, (float*)out, sink.T, sink.B, sink.HW, L, S, pad_action, t, ctx, Cs, runs, inv_fc, inv_pc);
+  MZ_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
 
 int mzba_sink_rep_input(const mzba_sink* sink, const uint8_t* frame0, int L, int pad_action, int t,
                         const int32_t* ctx, void* out, int out_bf16, int Cs, hipStream_t stream) {
-  MZ_CHECK_ARG(sink && sink->T > 0 && sink->B > 0 && sink->HW > 0 && sink->HW % 16 == 0 && sink->action &&
-               sink->frame && frame0 && out, -1);
-  MZ_CHECK_ARG(L >= 2 && Cs >= 2 * L && Cs % 8 == 0 && pad_action >= 0 && pad_action < 3, -1);
-  MZ_CHECK_ARG(ctx || (t >= 0 && t < sink->T), -1);
-  MZ_CHECK_ARG(aligned16(sink->frame) && aligned16(frame0) && aligned16(out), -1);  // 16-B loads and stores
-  const int S = (L + 7) / 8 * 8;
-  const size_t lds = (size_t)Cs * (out_bf16 ? 2 : 4) + (size_t)RUN * S + RUN / 16 * 8;
-  const int runs = (sink->HW + RUN - 1) / RUN;
-  const int ept = out_bf16 ? 8 : 4, FC = (L + ept - 1) / ept, PC = Cs / ept - FC;  // div_by's reciprocals
-  const uint32_t inv_fc = FC > 1 ? 0xffffffffu / (uint32_t)FC + 1u : 0u, inv_pc = PC > 1 ? 0xffffffffu / (uint32_t)PC + 1u : 0u;
-  MZ_CHECK_ARG(lds <= 64 * 1024 && (long long)sink->B * runs < (1LL << 31), -1);
-  const dim3 grid((unsigned)(sink->B * runs));
-  if (out_bf16)
-    hipLaunchKernelGGL(sink_rep_input_kernel<bf16_t>, grid, dim3(256), lds, stream, sink->action, sink->frame, frame0,
-                       (bf16_t*)out, sink->T, sink->B, sink->HW, L, S, pad_action, t, ctx, Cs, runs, inv_fc, inv_pc);
-  else
-    hipLaunchKernelGGL(sink_rep_input_kernel<float>, grid, dim3(256), lds, stream, sink->action, sink->frame, frame0,
-                       (float*)out, sink->T, sink->B, sink->HW, L, S, pad_action, t, ctx, Cs, runs, inv_fc, inv_pc);
+  MZ_CHECK_ARG(sink && frame0 && aligned16(frame0), -1);
+  return launch_sink_rep_input(*sink, FromFrame0{frame0}, L, pad_action, t, ctx, out, out_bf16, Cs, stream);
+}
+
+int mzba_sink_origin(const mzba_sink* sink, int32_t* origin, hipStream_t stream) {
+  MZ_CHECK_ARG(sink && sink->T > 0 && sink->B > 0 && sink->start && origin, -1);
+  hipLaunchKernelGGL(sink_origin_kernel, dim3((sink->B + 255) / 256), dim3(256), 0, stream, sink->start, origin, sink->T,
+                     sink->B);
   MZ_LAUNCH_CHECK();
   return 0;
+}
+
+int mzba_sink_rep_input_stream(const mzba_sink* sink, const int32_t* origin, int H, int W, int paddle_width,
+                               int brick_rows, int L, int pad_action, int t, const int32_t* ctx, void* out, int out_bf16,
+                               int Cs, hipStream_t stream) {
+  MZ_CHECK_ARG(sink && sink->start && origin && H > 0 && W > 0 && H <= 256 && W <= 256 && H * W == sink->HW, -1);
+  MZ_CHECK_ARG(paddle_width > 0 && paddle_width <= W && brick_rows > 0 && brick_rows <= H, -1);
+  return launch_sink_rep_input(*sink, FromOrigin{sink->start, origin, H, W, paddle_width, brick_rows}, L, pad_action, t,
+                               ctx, out, out_bf16, Cs, stream);
 }
 
 int mzba_record_results_masked(const int64_t* counts, const float* values, const mzba_sink* rec, int t,

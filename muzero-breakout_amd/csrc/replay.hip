@@ -259,7 +259,9 @@ __global__ __launch_bounds__(256) void stream_fill_kernel(ReplayRecords r, Strea
   if (b == r.B - 1 && si <= tb.nmax) tb.col(5)[si] = wo;
 }
 
-// one workgroup per window j in [j0, n): segment by binary search of the table's window offsets
+// one workgroup per window j in [j0, n): segment by binary search of the table's window offsets. FULL = false: the
+// same windows again after the sink's counts and values changed (write_window<false>; no frame is rendered)
+template <bool FULL>
 __global__ __launch_bounds__(256) void stream_write_kernel(ReplayRecords r, ReplayRing g, SegTable tb, int nseg, int H, int W,
                                                            int pw, int brick_rows, int K, int hist,
                                                            const float* __restrict__ dpow, int head, int j0) {
@@ -272,9 +274,9 @@ __global__ __launch_bounds__(256) void stream_write_kernel(ReplayRecords r, Repl
   }
   int paddle, bx, by;
   mz_start_unpack((uint32_t)tb.col(4)[lo], paddle, bx, by);
-  write_window(r, g, tb.col(0)[lo], tb.col(1)[lo], j - woff[lo], tb.col(2)[lo], __int_as_float(tb.col(3)[lo]),
-               ((size_t)head + j) % g.cap, K, hist, dpow,
-               [=](int q) { return mz_s0_chunk(q * 16, H, W, pw, brick_rows, paddle, bx, by); });
+  write_window<FULL>(r, g, tb.col(0)[lo], tb.col(1)[lo], j - woff[lo], tb.col(2)[lo], __int_as_float(tb.col(3)[lo]),
+                     ((size_t)head + j) % g.cap, K, hist, dpow,
+                     [=](int q) { return mz_s0_chunk(q * 16, H, W, pw, brick_rows, paddle, bx, by); });
 }
 
 // batch gather of window frames as f32 grayscale: out[n][hist][HW] = lut[code & 7]
@@ -383,9 +385,26 @@ int mzba_replay_stream_write(const mzba_sink* sink, int H, int W, int paddle_wid
   MZ_CHECK_ARG(n_segments > 0, -1);
   SegTable tb{const_cast<int32_t*>(table), nmax};
   const int j0 = n_windows > ring->cap ? n_windows - ring->cap : 0;  // older windows would be evicted at once
-  hipLaunchKernelGGL(stream_write_kernel, dim3(n_windows - j0), dim3(256), 0, stream, records(*sink, nullptr),
+  hipLaunchKernelGGL(stream_write_kernel<true>, dim3(n_windows - j0), dim3(256), 0, stream, records(*sink, nullptr),
                      ring_view(*ring), tb, n_segments, H, W, paddle_width, brick_rows, ring->K, ring->hist, dpow, head,
                      j0);
+  MZ_LAUNCH_CHECK();
+  return 0;
+}
+
+int mzba_replay_stream_rewrite(const mzba_sink* sink, const int32_t* table, int nmax, int n_segments, int n_windows,
+                               int j_first, const mzba_replay_ring* ring, int head, const float* dpow,
+                               hipStream_t stream) {
+  MZ_CHECK_ARG(sink && sink->T > 0 && sink->B > 0 && ring_ok(ring, head, n_windows) && j_first >= 0 &&
+               n_segments >= 0 && n_segments <= nmax && n_segments <= n_windows, -1);
+  MZ_CHECK_ARG(dpow && sink->reward && sink->counts && sink->values && table, -1);
+  int j0 = n_windows > ring->cap ? n_windows - ring->cap : 0;  // the windows the write kept
+  if (j_first > j0) j0 = j_first;                              // minus those evicted since
+  if (j0 >= n_windows) return 0;
+  MZ_CHECK_ARG(n_segments > 0, -1);
+  SegTable tb{const_cast<int32_t*>(table), nmax};
+  hipLaunchKernelGGL(stream_write_kernel<false>, dim3(n_windows - j0), dim3(256), 0, stream, records(*sink, nullptr),
+                     ring_view(*ring), tb, n_segments, 0, 0, 0, 0, ring->K, ring->hist, dpow, head, j0);
   MZ_LAUNCH_CHECK();
   return 0;
 }

@@ -103,6 +103,10 @@ SIGNATURES = {
     "mzba_sink_rep_input": [P, P, I, I, I, P, P, I, I, P],
     "mzba_record_results_masked": [P, P, P, I, P, P],
     "mzba_replay_rewrite": [P, P, P, P, P, I, I, P, I, P, P],
+    # ... of a streamed sink: the gather through the origin table, the rewrite through the segment table
+    "mzba_sink_origin": [P, P, P],
+    "mzba_sink_rep_input_stream": [P, P, I, I, I, I, I, I, I, P, P, I, I, P],
+    "mzba_replay_stream_rewrite": [P, P, I, I, I, I, P, I, P, P],
     # learner (learn.hip; mzba_conv_wpack / mzba_conv_pack_bf16* in pack.hip, mzba_conv_wgrad* in wgrad.hip)
     "mzba_bn_stats": [I, P, I, I, F, F, P, P, P, P, P, P, LL, P],
     "mzba_bn_apply": [I, P, P, P, I, P, I, I, P],

@@ -25,6 +25,9 @@ from .env import gray_lut
 # ingest's window 0, its window count (evicted-at-once ones included), the serial of window 0 (a count of every
 # window the buffer was given in its epoch, so it only grows) and that epoch (`empty_buffer` starts a new one).
 IngestHandle = collections.namedtuple("IngestHandle", "head n serial epoch")
+# The same for `ingest_stream` / `reingest_stream`, with the kept segments' count and what the ingest
+# planned with, so that the reingest plans the same table.
+StreamHandle = collections.namedtuple("StreamHandle", "head n segments serial epoch tail min_len episode_cap")
 
 
 def live_windows(serial, n, written, length):
@@ -68,10 +71,11 @@ class DeviceReplayBuffer:
         self.alpha, self.beta, self.prio_eps = float(alpha), float(beta), float(prio_eps)
         self._q = torch.zeros(cap, dtype=torch.float32, device=dev) if self.prioritized else None
         self._sample_ws = {}
-        # reanalyse bookkeeping: windows given to the ring in this epoch, the epoch, the last ingest_records' handle
+        # reanalyse bookkeeping: windows given to the ring in this epoch, the epoch, the last ingests' handles
         self._written = 0
         self._epoch = 0
         self.last_ingest = None
+        self.last_stream_ingest = None
 
     def __len__(self):
         return self.length
@@ -149,6 +153,20 @@ class DeviceReplayBuffer:
         self.length = min(total, cap)
         self.start = (self.start + total - self.length) % cap
 
+    def _plan_stream(self, rec, T, done, hlen, tail, min_len, episode_cap):
+        """The segment table of a streamed sink -> (sink, table, nmax, segments, windows). One host read."""
+        B = rec["action"].shape[1]
+        dev = self.device
+        nmax = B * (T // max(min_len + 1, self.K))
+        cnt = torch.empty(B, 2, dtype=torch.int32, device=dev)
+        offs = torch.empty(B + 1, 2, dtype=torch.int32, device=dev)
+        table = torch.empty(6, nmax + 1, dtype=torch.int32, device=dev)
+        sink = L.sink(rec, T, self.H * self.W)
+        L.call("mzba_replay_stream_plan", ctypes.byref(sink), L.ptr(done), L.ptr(hlen), self.K, min_len,
+               int(episode_cap), 1 if tail == "keep" else 0, L.ptr(cnt), L.ptr(offs), L.ptr(table), nmax, L.stream())
+        nseg, n = offs[B].tolist()
+        return sink, table, nmax, nseg, n
+
     def ingest_stream(self, rec, T, done, hlen, tail="drop", min_len=None, episode_cap=261, paddle_width=6,
                       brick_rows=3):
         """A streamed stage's sink (mzba.stream.StreamingStage): `rec` as for ingest_records plus rec["start"], the
@@ -157,29 +175,51 @@ class DeviceReplayBuffer:
         rendered from its start word, then its records. An env's last segment is closed iff done[b] or hlen[b] >=
         episode_cap; an open one is dropped (tail="drop") or ingested as a truncated trajectory (tail="keep"). Kept
         segments (length > min_len, default K + 1, and >= K) are saved by env, then by start row, so a sink with
-        one closed segment per env fills the ring exactly as ingest_records does. One host read. -> windows."""
+        one closed segment per env fills the ring exactly as ingest_records does. One host read. -> windows.
+        Leaves `last_stream` (the counts) and `last_stream_ingest` (the handle of a later `reingest_stream`)."""
         if tail not in ("drop", "keep"):
             raise ValueError("tail must be 'drop' or 'keep'")
         if rec.get("frame") is None or rec.get("start") is None:
             raise ValueError("ingest_stream needs the sink's recorded frames and start words")
         min_len = self.K + 1 if min_len is None else min_len
-        B = rec["action"].shape[1]
-        dev = self.device
-        nmax = B * (T // max(min_len + 1, self.K))
-        cnt = torch.empty(B, 2, dtype=torch.int32, device=dev)
-        offs = torch.empty(B + 1, 2, dtype=torch.int32, device=dev)
-        table = torch.empty(6, nmax + 1, dtype=torch.int32, device=dev)
-        sk = ctypes.byref(L.sink(rec, T, self.H * self.W))
-        L.call("mzba_replay_stream_plan", sk, L.ptr(done), L.ptr(hlen), self.K, min_len, int(episode_cap),
-               1 if tail == "keep" else 0, L.ptr(cnt), L.ptr(offs), L.ptr(table), nmax, L.stream())
-        nseg, n = offs[B].tolist()
+        sink, table, nmax, nseg, n = self._plan_stream(rec, T, done, hlen, tail, min_len, episode_cap)
         head = (self.start + self.length) % self.max_length
-        L.call("mzba_replay_stream_write", sk, self.H, self.W, paddle_width, brick_rows, L.ptr(table), nmax, nseg, n,
-               ctypes.byref(self._abi), head, L.ptr(self._powers(T)), L.stream())
+        L.call("mzba_replay_stream_write", ctypes.byref(sink), self.H, self.W, paddle_width, brick_rows, L.ptr(table),
+               nmax, nseg, n, ctypes.byref(self._abi), head, L.ptr(self._powers(T)), L.stream())
+        self.last_stream_ingest = StreamHandle(head, n, nseg, self._written, self._epoch, tail, min_len,
+                                               int(episode_cap))
         self._commit(head, n)
         # a segment of L records gives L - K + 1 windows: the kept rows are windows + segments * (K - 1)
         self.last_stream = {"segments": nseg, "windows": n}
         return n
+
+    def reingest_stream(self, handle, rec, T, done, hlen, paddle_width=6, brick_rows=3):
+        """`reingest_records` for a streamed sink: after the sink of an earlier `ingest_stream` (its
+        `last_stream_ingest` handle; the same rec layout and T, `done` / `hlen` as they were at that ingest,
+        Reanalyser.snapshot_stream keeps them) had its counts and values refreshed (Reanalyser.refresh_stream):
+        rewrite counts, values and n-step targets of the ingest's windows that are still in the ring, and with
+        prioritized=True their priorities by the ingest rule. The sink is planned again with the handle's tail,
+        min_len and episode_cap (mask, reward and start words are never written, so the table is the ingest's);
+        ValueError if it plans other segments or windows than the handle's. start and length do not change; the
+        ordering rules are reingest_records'. No frame is rendered: paddle_width and brick_rows, ingest_stream's
+        arguments, are accepted and not used. -> windows rewritten (0 for an evicted or pre-empty_buffer handle)."""
+        if handle is None or handle.epoch != self._epoch:
+            return 0
+        j_first, count = live_windows(handle.serial, handle.n, self._written, self.length)
+        if count == 0:
+            return 0
+        if rec.get("start") is None:
+            raise ValueError("reingest_stream needs the sink's start words")
+        sink, table, nmax, nseg, n = self._plan_stream(rec, T, done, hlen, handle.tail, handle.min_len,
+                                                       handle.episode_cap)
+        if (nseg, n) != (handle.segments, handle.n):
+            raise ValueError(f"reingest_stream: the sink plans {nseg} segments and {n} windows, the handle's ingest "
+                             f"wrote {handle.segments} and {handle.n}")
+        L.call("mzba_replay_stream_rewrite", ctypes.byref(sink), L.ptr(table), nmax, nseg, n, j_first,
+               ctypes.byref(self._abi), handle.head, L.ptr(self._powers(T)), L.stream())
+        if self.prioritized:  # the ingest rule over slots (head + j) % cap, j in [j_first, n)
+            self._init_priorities((handle.head + j_first) % self.max_length, n - j_first)
+        return count
 
     def save_observation_trajectory(self, observation_trajectory):
         """replay_buffer.py:96-165 for one host trajectory (padded as _pad_initial_state builds it)."""

@@ -96,6 +96,7 @@ class StreamingStage:
         loop.restart = self._restart
         self.use_graph = use_graph
         self.ep_base = 0
+        self.last_search_id0 = None  # the search id of row 0 of the last stage run
 
     def _restart(self, loop):
         loop.env.restart(loop.rec["start"], loop.ctx, self.blk)
@@ -119,6 +120,7 @@ class StreamingStage:
         self.blk.copy_(torch.tensor([self.ep_base, self.episode_cap], dtype=torch.int32))
         loop.reset(self.ep_base)
         self.ep_base += self.steps  # this stage's restarts use the keys in between
+        self.last_search_id0 = loop.search_id  # row t of this stage is searched under this id + t (reanalyse)
         for _ in range(self.steps):
             loop.act()
             if self.use_graph and loop.graph is None and loop.inject_noise is None and loop.noise_log is None:
