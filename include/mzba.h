@@ -329,6 +329,18 @@ int mzba_replay_stream_plan(const mzba_sink* sink, const uint8_t* done, const in
 int mzba_replay_stream_write(const mzba_sink* sink, int H, int W, int paddle_width, int brick_rows,
                              const int32_t* table, int nmax, int n_segments, int n_windows,
                              const mzba_replay_ring* ring, int head, const float* dpow, hipStream_t stream);
+/* stream_gather (the sink archive): stream_write for a list of n windows, one workgroup each, bit-equal
+ *   rows. Window j = idx[i] goes to ring row slot0 + i (no modulo; slot0 < 0 or slot0 + n > cap is -1). idx NULL draws
+ *   j = ((u64)x * N) >> 32, x = the .x word of Philox (i, stream 6, step, 0) under seed, step = step_dev ? step_dev[0]
+ *   : step (device u32 [1]). totals i32 [2] = {segments, windows = N} on the device (stream_plan's offs[B]): a captured
+ *   launch follows a table planned again at the same addresses. j outside [0, N), N <= 0 or segments <= 0: nothing
+ *   of the sink or of the table's body is read and the row is not written. idx_out (optional, i32 [n]) = j, or -1 for
+ *   a skipped window. n == 0: 0, no launch. A sink with T * B >= 2^31 is refused (-1); the other checks are
+ *   stream_write's. */
+int mzba_replay_stream_gather(const mzba_sink* sink, int H, int W, int paddle_width, int brick_rows,
+                              const int32_t* table, int nmax, const int32_t* totals, const int32_t* idx, int n,
+                              uint64_t seed, uint32_t step, const uint32_t* step_dev, const mzba_replay_ring* ring,
+                              int slot0, const float* dpow, int32_t* idx_out, hipStream_t stream);
 
 /* ===================== prioritized replay (MuZero, Appendix G; csrc/replay_prio.hip)
  * q f32[cap], 16-byte aligned, in slot space: q[slot] = p^alpha for a live window, exactly 0 for a slot that

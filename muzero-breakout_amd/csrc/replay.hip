@@ -12,7 +12,8 @@
 //                        of fixed-size rows (frames stay u8 codes: 10 KB per window at 16x20);
 //   replay_states_kernel: gathers a batch of windows' frames as f32 grayscale (the learner's input).
 // A streamed sink (several episodes per env) goes through stream_count / stream_scan / stream_fill
-// (a flat segment table) and stream_write_kernel, which shares write_window with replay_write_kernel.
+// (a flat segment table) and stream_write_kernel, which shares write_window with replay_write_kernel;
+// stream_gather_kernel writes a list of the table's windows, given or drawn, for the sink archive.
 #include "common.h"
 
 namespace {
@@ -259,6 +260,30 @@ __global__ __launch_bounds__(256) void stream_fill_kernel(ReplayRecords r, Strea
   if (b == r.B - 1 && si <= tb.nmax) tb.col(5)[si] = wo;
 }
 
+// the last segment of woff[0, nseg) with woff[seg] <= j (nseg > 0)
+MZ_DEV int segment_of(const int32_t* __restrict__ woff, int nseg, int j) {
+  int lo = 0, hi = nseg;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (woff[mid] <= j) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// window j of the table -> ring row `slot`: the body of both streamed writers
+template <bool FULL>
+MZ_DEV void write_table_window(const ReplayRecords& r, const ReplayRing& g, const SegTable& tb, int nseg, int j,
+                               size_t slot, int H, int W, int pw, int brick_rows, int K, int hist,
+                               const float* __restrict__ dpow) {
+  const int32_t* woff = tb.col(5);
+  const int lo = segment_of(woff, nseg, j);
+  int paddle, bx, by;
+  mz_start_unpack((uint32_t)tb.col(4)[lo], paddle, bx, by);
+  write_window<FULL>(r, g, tb.col(0)[lo], tb.col(1)[lo], j - woff[lo], tb.col(2)[lo], __int_as_float(tb.col(3)[lo]),
+                     slot, K, hist, dpow,
+                     [=](int q) { return mz_s0_chunk(q * 16, H, W, pw, brick_rows, paddle, bx, by); });
+}
+
 // one workgroup per window j in [j0, n): segment by binary search of the table's window offsets. FULL = false: the
 // same windows again after the sink's counts and values changed (write_window<false>; no frame is rendered)
 template <bool FULL>
@@ -266,17 +291,38 @@ __global__ __launch_bounds__(256) void stream_write_kernel(ReplayRecords r, Repl
                                                            int pw, int brick_rows, int K, int hist,
                                                            const float* __restrict__ dpow, int head, int j0) {
   const int j = j0 + blockIdx.x;
-  const int32_t* woff = tb.col(5);
-  int lo = 0, hi = nseg;  // last segment with woff[seg] <= j
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (woff[mid] <= j) lo = mid; else hi = mid;
+  write_table_window<FULL>(r, g, tb, nseg, j, ((size_t)head + j) % g.cap, H, W, pw, brick_rows, K, hist, dpow);
+}
+
+// The archive's draw: Philox (request i, stream 6, step, 0). Streams 0-3 are in common.h, 4 in
+// replay_prio.hip, 5 in gumbel.hip.
+constexpr int MZ_STREAM_ARCHIVE = 6;
+
+// stream_write_kernel for a list of windows: workgroup i writes window j = idx[i] of the table into ring row
+// slot0 + i; without idx, j = (x * N) >> 32 with x the full 32-bit Philox word (N may exceed 2^24). The segment and
+// window counts are read from totals = {segments, windows} (stream_plan's offs[B]) on the device, so a captured
+// launch follows a table that is planned again. A window outside [0, N), or an empty table, returns before any read
+// of the sink or of the table's body and leaves its ring row alone; idx_out (optional) gets j, or -1 for those.
+__global__ __launch_bounds__(256) void stream_gather_kernel(ReplayRecords r, ReplayRing g, SegTable tb,
+                                                            const int32_t* __restrict__ totals,
+                                                            const int32_t* __restrict__ idx, uint64_t seed, uint32_t step,
+                                                            const uint32_t* __restrict__ step_dev, int H, int W, int pw,
+                                                            int brick_rows, int K, int hist,
+                                                            const float* __restrict__ dpow, int slot0,
+                                                            int32_t* __restrict__ idx_out) {
+  const int i = blockIdx.x;
+  const int nseg = totals[0], N = totals[1];
+  int j = -1;
+  if (idx) {
+    j = idx[i];
+  } else if (N > 0) {
+    if (step_dev) step = step_dev[0];
+    j = (int)(((uint64_t)mz_u32((uint32_t)i, MZ_STREAM_ARCHIVE, step, 0, seed) * (uint32_t)N) >> 32);
   }
-  int paddle, bx, by;
-  mz_start_unpack((uint32_t)tb.col(4)[lo], paddle, bx, by);
-  write_window<FULL>(r, g, tb.col(0)[lo], tb.col(1)[lo], j - woff[lo], tb.col(2)[lo], __int_as_float(tb.col(3)[lo]),
-                     ((size_t)head + j) % g.cap, K, hist, dpow,
-                     [=](int q) { return mz_s0_chunk(q * 16, H, W, pw, brick_rows, paddle, bx, by); });
+  const bool ok = nseg > 0 && nseg <= tb.nmax && N > 0 && j >= 0 && j < N;
+  if (idx_out && threadIdx.x == 0) idx_out[i] = ok ? j : -1;
+  if (!ok) return;
+  write_table_window<true>(r, g, tb, nseg, j, (size_t)slot0 + i, H, W, pw, brick_rows, K, hist, dpow);
 }
 
 // batch gather of window frames as f32 grayscale: out[n][hist][HW] = lut[code & 7]
@@ -388,6 +434,26 @@ int mzba_replay_stream_write(const mzba_sink* sink, int H, int W, int paddle_wid
   hipLaunchKernelGGL(stream_write_kernel<true>, dim3(n_windows - j0), dim3(256), 0, stream, records(*sink, nullptr),
                      ring_view(*ring), tb, n_segments, H, W, paddle_width, brick_rows, ring->K, ring->hist, dpow, head,
                      j0);
+  MZ_LAUNCH_CHECK();
+  return 0;
+}
+
+int mzba_replay_stream_gather(const mzba_sink* sink, int H, int W, int paddle_width, int brick_rows,
+                              const int32_t* table, int nmax, const int32_t* totals, const int32_t* idx, int n,
+                              uint64_t seed, uint32_t step, const uint32_t* step_dev, const mzba_replay_ring* ring,
+                              int slot0, const float* dpow, int32_t* idx_out, hipStream_t stream) {
+  MZ_CHECK_ARG(sink && sink->T > 0 && sink->B > 0 && H > 0 && W > 0 && H <= 256 && W <= 256 && (H * W) % 16 == 0 &&
+               sink->HW == H * W && ring_ok(ring, 0, n) && nmax >= 0, -1);
+  // rows, and with them windows (a segment of L rows gives at most L), are indexed in 32 bits
+  MZ_CHECK_ARG((long long)sink->T * sink->B <= 0x7fffffffLL, -1);
+  MZ_CHECK_ARG(slot0 >= 0 && (long long)slot0 + n <= ring->cap, -1);  // row slot0 + i: no modulo
+  MZ_CHECK_ARG(dpow && sink->action && sink->reward && sink->counts && sink->values && sink->frame && table && totals,
+               -1);
+  if (n == 0) return 0;
+  SegTable tb{const_cast<int32_t*>(table), nmax};
+  hipLaunchKernelGGL(stream_gather_kernel, dim3(n), dim3(256), 0, stream, records(*sink, nullptr), ring_view(*ring), tb,
+                     totals, idx, seed, step, step_dev, H, W, paddle_width, brick_rows, ring->K, ring->hist, dpow, slot0,
+                     idx_out);
   MZ_LAUNCH_CHECK();
   return 0;
 }

@@ -70,6 +70,8 @@ SIGNATURES = {
     "mzba_env_restart_compact": [P, P, P, P, U64, I, P, I, P],
     "mzba_replay_stream_plan": [P, P, P, I, I, I, I, P, P, P, I, P],
     "mzba_replay_stream_write": [P, I, I, I, I, P, I, I, I, P, I, P, P],
+    # the sink archive's window gather (replay.hip)
+    "mzba_replay_stream_gather": [P, I, I, I, I, P, I, P, P, I, U64, U32, P, P, I, P, P, P],
     # prioritized replay (replay_prio.hip)
     "mzba_replay_priority_init": [P, P, P, I, I, I, I, F, F, P],
     "mzba_replay_priority_update": [P, P, P, I, I, F, F, P],
