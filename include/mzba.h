@@ -375,6 +375,37 @@ int mzba_replay_sample(const float* q, int cap, int n, float beta, int n_live, u
                        const uint32_t* step_dev, const float* u_in, int32_t* slots, float* prob, float* weight,
                        void* ws, long long ws_bytes, hipStream_t stream);
 
+/* ===================== prioritized replay over the sink archive (csrc/archive_prio.hip)
+ * q f32[n_rows], n_rows = T * B < 2^31, 16-byte aligned, in sink-row space (row * B + env): q = p^alpha at the root
+ * record of every window of a kept segment, exactly 0 at every other row. table / nmax / offs / totals are
+ * stream_plan's table, its capacity, its exclusive scan offs i32 [B + 1][2] and offs[B] = {segments, windows}.
+ * archive_row_windows: idx_out[j] = the window whose root record is sink row rows[j], or -1. Env b = row % B owns
+ *   the table entries [offs[2 b], offs[2 b + 2]); the last of them with start row t0 <= t = row / B gives s = t - t0,
+ *   a root iff s <= L - K, window woff + s. A row outside [0, n_rows), segments outside [1, nmax] and an empty range
+ *   return -1 before any read of the table's body.
+ * archive_priority_init: one thread per (row, env) of rows [row0, row0 + nrows) of the sink: a root gets
+ *   q = (|values[row] - z| + eps)^alpha, z = the n-step target of its window's position 0 (stream_write's statements,
+ *   dpow as there), every other row 0. Reads the sink's reward and values.
+ * archive_sample: mzba_replay_sample's stratified inverse-CDF over rows, with a three-level f64 prefix (1024 rows per
+ *   block, 1024 blocks per super-block, <= 2048 super-block sums; fixed order, no atomics, the same bits on every
+ *   run). u_j = u_in[j] (f64) or (x0 2^21 + (x1 >> 11)) 2^-53 from the first two words of Philox (j, stream 7, step, 0)
+ *   under seed, step = step_dev ? step_dev[0] : step; t_j = ((j + u_j) / n) S in f64. rows[j] = the row, idx[j] =
+ *   its window by the lookup (table NULL: the plain row sampler, idx optional and -1, N = n_live > 0 or -3),
+ *   prob[j] = q / S, weight[j] = (N prob)^-beta over the batch's largest, N = totals[1] read on the device. A drawn
+ *   row that is no root, S == 0 and N <= 0 give rows = idx = -1, prob = weight = 0, left out of the largest.
+ *   n <= 2^20; ws >= mzba_archive_sample_ws_bytes(n_rows, n) bytes, 16-byte aligned (-2). Five launches, no host
+ *   synchronisation. Priorities are rewritten with mzba_replay_priority_update(_g), slots = rows, cap = n_rows. */
+int mzba_archive_row_windows(const int32_t* table, int nmax, const int32_t* offs, const int32_t* totals, int B, int K,
+                             int n_rows, const int32_t* rows, int n, int32_t* idx_out, hipStream_t stream);
+int mzba_archive_priority_init(const mzba_sink* sink, const int32_t* table, int nmax, const int32_t* offs,
+                               const int32_t* totals, float* q, int row0, int nrows, int K, const float* dpow,
+                               float alpha, float eps, hipStream_t stream);
+long long mzba_archive_sample_ws_bytes(int n_rows, int n);
+int mzba_archive_sample(const float* q, int n_rows, int n, float beta, int n_live, const int32_t* table, int nmax,
+                        const int32_t* offs, const int32_t* totals, int B, int K, uint64_t seed, uint32_t step,
+                        const uint32_t* step_dev, const double* u_in, int32_t* rows, int32_t* idx, float* prob,
+                        float* weight, void* ws, long long ws_bytes, hipStream_t stream);
+
 /* kernel choice for experiments/tests: 0 by batch (default), 1 four-env 8-wave kernel, 2 eight-env
  * kernel, 3 four-env 4-wave kernel */
 int mzba_tower_set_variant(int v);

@@ -14,20 +14,9 @@
 // A streamed sink (several episodes per env) goes through stream_count / stream_scan / stream_fill
 // (a flat segment table) and stream_write_kernel, which shares write_window with replay_write_kernel;
 // stream_gather_kernel writes a list of the table's windows, given or drawn, for the sink archive.
-#include "common.h"
+#include "replay_dev.h"
 
 namespace {
-
-struct ReplayRecords {
-  const uint8_t* action;   // [T][B]
-  const float* reward;     // [T][B]
-  const uint8_t* mask;     // [T][B] recorded (not prev_done)
-  const int64_t* counts;   // [T][B][3]
-  const float* value;      // [T][B]
-  const uint8_t* frame;    // [T][B][HW]
-  const uint8_t* frame0;   // [B][HW]
-  int T, B, HW;
-};
 
 struct ReplayRing {
   int64_t* past_actions;   // [cap][hist]
@@ -104,18 +93,7 @@ MZ_DEV void write_window(const ReplayRecords& r, const ReplayRing& g, int b, int
     }
     g.values[slot * K + i] = r.value[(size_t)t * B + b];
     for (int a = 0; a < 3; ++a) g.counts[(slot * K + i) * 3 + a] = (float)r.counts[((size_t)t * B + b) * 3 + a];
-    // n-step target (replay_buffer.py:137-151): bootstrap td_steps = 10 ahead, scaled by
-    // discount**K; dpow[k] = f32(discount**k) (python double pow, host table), dpow[T + 1] = f32(discount**K)
-    const int cur = s + i, boot = s + 10 + i;
-    float v;
-    if (boot < L) {
-      v = r.value[(size_t)(t0 + boot) * B + b] * dpow[r.T + 1];
-      for (int k = 0; k < boot - cur; ++k) v = v + dpow[k] * r.reward[(size_t)(t0 + cur + k) * B + b];
-    } else {
-      v = dpow[0] * r.reward[(size_t)(t0 + cur) * B + b];  // python 0.0 + the first term is that term
-      for (int k = 1; k < L - cur; ++k) v = v + dpow[k] * r.reward[(size_t)(t0 + cur + k) * B + b];
-    }
-    g.targets[slot * K + i] = v;
+    g.targets[slot * K + i] = nstep_target(r, b, t0, s + i, L, dpow);
   } else if (FULL && tid == hist + K) {
     g.reward_sum[slot] = rsum;
   }
@@ -237,13 +215,6 @@ __global__ __launch_bounds__(PT) void stream_scan_kernel(const int32_t* __restri
   if (tid == PT - 1) { offs[2 * B] = ps[PT - 1]; offs[2 * B + 1] = pw[PT - 1]; }
 }
 
-// the flat segment table, six columns of nmax + 1 words: env, start row, length, reward sum (f32 bits), start word,
-// window offset (exclusive scan over the kept segments; entry [number of segments] = the number of windows)
-struct SegTable {
-  int32_t* w; int nmax;
-  MZ_DEV int32_t* col(int k) const { return w + (size_t)k * (nmax + 1); }
-};
-
 // one thread per env: its kept segments into the table from offs[b] on
 __global__ __launch_bounds__(256) void stream_fill_kernel(ReplayRecords r, StreamPlan p, const int32_t* __restrict__ offs,
                                                           SegTable tb) {
@@ -343,10 +314,7 @@ __global__ __launch_bounds__(256) void replay_states_kernel(const uint8_t* __res
   }
 }
 
-// the kernels' views of the ABI's sink and ring (include/mzba.h)
-ReplayRecords records(const mzba_sink& s, const uint8_t* frame0) {
-  return {s.action, s.reward, s.mask, s.counts, s.values, s.frame, frame0, s.T, s.B, s.HW};
-}
+// the kernels' view of the ABI's ring (include/mzba.h); records() of its sink is in replay_dev.h
 ReplayRing ring_view(const mzba_replay_ring& g) {
   return {g.past_actions, g.future_actions, g.states, g.rewards, g.counts, g.values, g.targets, g.reward_sum, g.cap};
 }

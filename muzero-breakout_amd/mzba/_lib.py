@@ -77,6 +77,11 @@ SIGNATURES = {
     "mzba_replay_priority_update": [P, P, P, I, I, F, F, P],
     "mzba_replay_sample_ws_bytes": [I, I],
     "mzba_replay_sample": [P, I, I, F, I, U64, U32, P, P, P, P, P, P, LL, P],
+    # ... over the sink archive, in sink-row space (archive_prio.hip)
+    "mzba_archive_row_windows": [P, I, P, P, I, I, I, P, I, P, P],
+    "mzba_archive_priority_init": [P, P, I, P, P, P, I, I, I, P, F, F, P],
+    "mzba_archive_sample_ws_bytes": [I, I],
+    "mzba_archive_sample": [P, I, I, F, I, P, I, P, P, I, I, U64, U32, P, P, P, P, P, P, P, LL, P],
     "mzba_conv_band": [P, P, P, P, P, I, I, I, I, I, I, P],
     "mzba_conv_band_res_supported": [I, I, I],
     "mzba_conv_band_res": [P, P, P, P, P, P, I, I, I, I, P],
@@ -219,6 +224,7 @@ GUMBEL_STRUCTS = {"mzba_gumbel": Gumbel}
 # entry points that return something other than a status code
 RESTYPES = {"mzba_tower_ws_bytes": LL, "mzba_tower_plan": I, "mzba_conv_lat_get_variant": I, "mzba_conv_wgrad_ws_bytes": LL,
             "mzba_linear_ws_bytes": LL, "mzba_learner_loss_ws_bytes": LL, "mzba_replay_sample_ws_bytes": LL,
+            "mzba_archive_sample_ws_bytes": LL,
             "mzba_grad_stats_ws_bytes": LL}
 
 

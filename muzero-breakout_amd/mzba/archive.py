@@ -10,6 +10,11 @@ drawn on the device, into a small ring-shaped staging area the learner trains fr
     losses = archive.training_stage(learner, num_batches, minibatch_size)
     archive.refresh(reanalyser, slab)                        # reanalyse: nothing follows, the next gather sees it
 
+`prioritized=True` adds prioritized replay in sink-row space (csrc/archive_prio.hip): a priority per
+sink row, set at `append` and `refresh` from |searched value - n-step target|, a device sampler of rows (`sample`) and
+the learner's write-back (`update_priorities`); `prioritized_view(B)` lets an unedited `Learner` run its prioritized
+step from the archive.
+
 A gathered window is bit-equal to the one `ingest_stream` writes (csrc/replay.hip: mzba_replay_stream_gather runs
 mzba_replay_stream_write's window body). Opt-in: nothing else of the package uses it.
 """
@@ -62,11 +67,15 @@ class SinkArchive:
     hlen[b] >= episode_cap, `ingest_stream`'s rule), with tail="keep" nothing is. The archive is then planned with
     every last segment closed.
 
-    Not supported: prioritized sampling (window indices move at every append), lockstep (`frame0`) sinks, sharded
-    sinks, an open tail carried into the next stage."""
+    prioritized=True keeps q f32[T * B] beside the sink, indexed row * B + env: (|value - n-step target| + prio_eps)
+    ** alpha at the root record of every window, exactly 0 at every other row. A root's row does not move when other
+    slabs are appended; the sampler draws rows and looks their windows up in the table of the moment. The one
+    ordering rule, as for the ring: no `append` or `refresh` between a `sample` and its `update_priorities`.
+
+    Not supported: lockstep (`frame0`) sinks, sharded sinks, an open tail carried into the next stage."""
 
     def __init__(self, slabs, steps, B, K, seq_len, discount, height=16, width=20, min_len=None, episode_cap=261,
-                 paddle_width=6, brick_rows=3, device="cuda"):
+                 paddle_width=6, brick_rows=3, device="cuda", prioritized=False, alpha=1.0, beta=1.0, prio_eps=1e-3):
         L.require_gpu()
         if slabs < 1 or steps < 1 or B < 1:
             raise ValueError("SinkArchive: slabs, steps and B must be positive")
@@ -107,6 +116,11 @@ class SinkArchive:
         self.search_id0 = [None] * self.slabs
         self.draw_step = 0    # the Philox step of training_stage's next gather
         self._staged = {}
+        self.prioritized = bool(prioritized)
+        self.alpha, self.beta, self.prio_eps = float(alpha), float(beta), float(prio_eps)
+        self._q = torch.zeros(T * B, dtype=torch.float32, device=dev) if self.prioritized else None
+        self._sample_ws = {}
+        self._views = {}
 
     def __len__(self):
         return self.windows
@@ -151,6 +165,8 @@ class SinkArchive:
         self.segments, self.windows = self._totals.tolist()
         self.search_id0[slab] = search_id0
         self.appended += 1
+        if self.prioritized:  # the evicted stage's priorities go, the other slabs' learned ones stay
+            self.reprioritize(slab)
         return slab
 
     def append_stage(self, stage, tail="drop"):
@@ -200,12 +216,21 @@ class SinkArchive:
         slots = torch.arange(slot0, slot0 + n, dtype=torch.int32, device=self.device)
         return st, slots, idx_out
 
-    def training_stage(self, learner, num_batches, minibatch_size, seed=0):
+    def training_stage(self, learner, num_batches, minibatch_size, seed=0, prioritized=False):
         """num_batches minibatches of drawn windows: one gather of num_batches * minibatch_size windows under the
         archive's own draw step (advanced here, so no two stages share draws), then learner.train_minibatch on each
         chunk of the staged rows (the learner's captured graph where one was captured for that holder:
         learner.capture(archive.staged(num_batches * minibatch_size), minibatch_size)). The only host read is that
-        of the losses at the end. -> the per-minibatch losses (host floats)."""
+        of the losses at the end. -> the per-minibatch losses (host floats).
+
+        prioritized=True: num_batches prioritized steps instead (learner.prioritized_step on
+        prioritized_view(minibatch_size): sample rows, gather their windows, the weighted minibatch, update the
+        rows' priorities; the captured graph where learner.capture(view, minibatch_size, prioritized=True, seed) was
+        called), under the learner's own step counter."""
+        if prioritized:
+            view = self.prioritized_view(minibatch_size)
+            losses = [learner.prioritized_step(view, minibatch_size, seed).clone() for _ in range(num_batches)]
+            return [float(x[0]) for x in losses]
         n = int(num_batches) * int(minibatch_size)
         st, slots, _ = self.gather(n, step=self.draw_step, seed=seed)
         self.draw_step += 1
@@ -225,5 +250,127 @@ class SinkArchive:
             raise ValueError(f"SinkArchive.refresh: slab {slab} holds no stage")
         if self.search_id0[slab] is None:
             raise ValueError(f"SinkArchive.refresh: slab {slab} was appended without its search_id0")
-        return reanalyser.refresh_stream(self.slab_rec(slab), self.steps, self.search_id0[slab], rows=rows,
-                                         noise_weight=noise_weight, use_graph=use_graph)
+        n = reanalyser.refresh_stream(self.slab_rec(slab), self.steps, self.search_id0[slab], rows=rows,
+                                      noise_weight=noise_weight, use_graph=use_graph)
+        if self.prioritized:  # Appendix G: reanalyse writes priorities
+            self.reprioritize(slab)
+        return n
+
+    # -- prioritized replay in sink-row space (csrc/archive_prio.hip) -----------------------
+    def _need_prio(self):
+        if not self.prioritized:
+            raise RuntimeError("this SinkArchive was built with prioritized=False")
+
+    def reprioritize(self, slab):
+        """The init rule over the rows of one slab: q = (|value - n-step target| + prio_eps) ** alpha at every root
+        record, 0 elsewhere, from the sink and the plan as they are now. `append` and `refresh` call it."""
+        self._need_prio()
+        slab = int(slab)
+        if not 0 <= slab < self.slabs:
+            raise ValueError(f"SinkArchive.reprioritize: no slab {slab}")
+        L.call("mzba_archive_priority_init", ctypes.byref(self._sink), L.ptr(self._table), self.nmax,
+               L.ptr(self._offs), L.ptr(self._totals), L.ptr(self._q), slab * self.steps, self.steps, self.K,
+               L.ptr(self._dpow), self.alpha, self.prio_eps, L.stream())
+
+    def _sample_workspace(self, n):
+        """The sampler's scratch for n samples, kept per n (allocate it before a graph capture that samples)."""
+        self._need_prio()
+        ws = self._sample_ws.get(n)
+        if ws is None:
+            nbytes = L.lib().mzba_archive_sample_ws_bytes(self.T * self.B, n)
+            ws = self._sample_ws[n] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def sample(self, n, step, seed=0, u=None, step_dev=None):
+        """n windows drawn in proportion to their priorities (stratified: sample j from the j-th n-th of the mass), on
+        the device with no host round trip -> (rows i32[n] sink rows row * B + env, idx i32[n] their windows for
+        `gather`, weights f32[n] = (windows * P) ** -beta over the batch's largest, probs f32[n]). The draws are 53-bit
+        Philox uniforms (j, stream 7, step, 0) under `seed`; `step_dev` (device i32/u32 [1]) overrides `step`; `u`
+        (device f64[n] in [0, 1)) replaces the draws. The window count is read on the device, so a captured sample
+        follows later appends. A draw that cannot be used (no priority mass; a row that is no root any more) gives
+        rows = idx = -1 and weight 0."""
+        self._need_prio()
+        n, dev = int(n), self.device
+        rows = torch.empty(n, dtype=torch.int32, device=dev)
+        idx = torch.empty(n, dtype=torch.int32, device=dev)
+        probs = torch.empty(n, dtype=torch.float32, device=dev)
+        weights = torch.empty(n, dtype=torch.float32, device=dev)
+        if u is not None:
+            u = u.to(device=dev, dtype=torch.float64).contiguous()
+            if u.numel() != n:
+                raise ValueError("u must hold one draw per sample")
+        if step_dev is not None and (step_dev.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32))
+                                     or not step_dev.is_cuda):
+            raise ValueError("step_dev must be a device int32 / uint32 tensor")
+        ws = self._sample_workspace(n)
+        L.call("mzba_archive_sample", L.ptr(self._q), self.T * self.B, n, self.beta, 0, L.ptr(self._table), self.nmax,
+               L.ptr(self._offs), L.ptr(self._totals), self.B, self.K, int(seed), int(step) & 0xFFFFFFFF,
+               L.ptr(step_dev), L.ptr(u), L.ptr(rows), L.ptr(idx), L.ptr(probs), L.ptr(weights), L.ptr(ws), ws.numel(),
+               L.stream())
+        return rows, idx, weights, probs
+
+    def update_priorities(self, rows, td, guard_block=None):
+        """q[rows[j]] = (td[j] + prio_eps) ** alpha (td: the learner's last_td for the windows of a `sample`; a row of
+        -1 is skipped). No append or refresh may run between the sample and this call; duplicates are the same
+        window and carry equal td. guard_block (a guarded Learner's device stats block): q stays as it is when that
+        step was skipped."""
+        self._need_prio()
+        if rows.dtype != torch.int32 or td.dtype != torch.float32 or rows.numel() != td.numel():
+            raise ValueError("update_priorities takes i32 rows and f32 td of one length")
+        rows, td = rows.contiguous(), td.contiguous()  # held until the launch is made
+        if guard_block is not None:
+            L.call("mzba_replay_priority_update_g", L.ptr(self._q), L.ptr(rows), L.ptr(td), rows.numel(),
+                   self.T * self.B, self.alpha, self.prio_eps, L.ptr(guard_block), L.stream())
+            return
+        L.call("mzba_replay_priority_update", L.ptr(self._q), L.ptr(rows), L.ptr(td), rows.numel(), self.T * self.B,
+               self.alpha, self.prio_eps, L.stream())
+
+    def root_rows(self):
+        """Sink row (row * B + env, device i64) of every window's root record, in archive window order."""
+        ns = self.segments
+        env, t0, ln, woff = (self._table[k, :ns].long() for k in (0, 1, 2, 5))
+        seg = torch.repeat_interleave(torch.arange(ns, device=self.device), ln - self.K + 1)
+        s = torch.arange(seg.numel(), device=self.device) - woff[seg]
+        return (t0[seg] + s) * self.B + env[seg]
+
+    def priorities(self):
+        """q = p ** alpha at the windows' root records, in archive window order (f32 device tensor)."""
+        self._need_prio()
+        return self._q[self.root_rows()]
+
+    def prioritized_view(self, B):
+        """The ring-shaped object (one per B, kept) that runs an unedited Learner's prioritized step from the archive:
+        Learner.capture(view, B, prioritized=True, seed), Learner.prioritized_step(view, B, seed),
+        Learner.training_stage(view, ..., prioritized=True)."""
+        self._need_prio()
+        view = self._views.get(B)
+        if view is None:
+            view = self._views[B] = PrioritizedView(self, int(B))
+        return view
+
+
+class PrioritizedView:
+    """`SinkArchive.staged(B)` with a prioritized ring's sampling surface: `sample` draws B rows of the archive,
+    gathers their windows into the staged rows 0 .. B - 1 and remembers the rows; `update_priorities` writes to them.
+    An unusable draw (weight 0) leaves its staged row as it was."""
+
+    def __init__(self, archive, B):
+        self.archive, self.B = archive, B
+        self.staged = archive.staged(B)
+        self._ring, self._abi = self.staged._ring, self.staged._abi
+        self._slots = torch.arange(B, dtype=torch.int32, device=archive.device)
+        self.rows = None
+
+    def _sample_workspace(self, B):
+        return self.archive._sample_workspace(B)
+
+    def sample(self, B, step, seed=0, step_dev=None):
+        if B != self.B:
+            raise ValueError(f"this view stages {self.B} windows, not {B}")
+        rows, idx, weights, probs = self.archive.sample(B, step, seed=seed, step_dev=step_dev)
+        self.archive.gather(B, idx=idx, out=self.staged)
+        self.rows = rows
+        return self._slots, weights, probs
+
+    def update_priorities(self, slots, td, guard_block=None):
+        self.archive.update_priorities(self.rows, td, guard_block=guard_block)
