@@ -181,6 +181,10 @@ class Learner:
         self.per_step = 0         # prioritized steps taken: the sampler's Philox step
         self.last_td = self.last_slots = self.last_weights = None
         self._capturing = False
+        # keep_tape (tests, eager only): a minibatch leaves `last_tape`, the tensors it computed with — what the f64
+        # replay of tests/learner_tape.py audits. Off: the launches of before and nothing kept.
+        self.keep_tape = False
+        self.last_tape = None
         if dtype not in ("f32", "bf16"):
             raise ValueError("dtype must be 'f32' or 'bf16'")
         self.m, self.K, self.device = mcfg, K, torch.device(device)
@@ -951,6 +955,8 @@ class Learner:
             # the side stream must exist (default priority, created by an eager minibatch) before
             # capture: no stream is created or re-prioritised inside torch.cuda.graph
             raise RuntimeError("Learner.capture: run one eager minibatch of this size first")
+        if self.keep_tape:
+            raise RuntimeError("Learner.capture: keep_tape is eager only (a graph's activations live in its pool)")
         self._graph = None
         self._g_prio, self._g_seed = bool(prioritized), int(seed)
         self._g_slots = torch.zeros(B, dtype=torch.int32, device=self.device)
@@ -1071,6 +1077,12 @@ class Learner:
             unroll.append((pu, du))
         self._join(*crossing)
         self._settle()  # every BN output the backward reads exists
+        # the tape (keep_tape): references only forward — the backward reads the stored forward tensors and writes
+        # none of them (gradients are overwritten in place); the gradient checkpoints below are clones
+        tape = None
+        if self.keep_tape and not self._capturing:
+            tape = dict(x=x, rep_saved=rep_saved, latents=[t for t in crossing[2:]] + [h.t], unroll=list(unroll),
+                        gps=[None] * K, dh=[None] * K)
         # ---- loss_fn
         dlr, dlv, dlp = torch.empty_like(lr_all), torch.empty_like(lv_all), torch.empty_like(lp_all)
         loss = torch.empty(4, device=self.device)
@@ -1087,6 +1099,9 @@ class Learner:
             self.last_td = torch.empty(B, dtype=torch.float32, device=self.device)
             L.call("mzba_learner_loss_w", *largs, L.ptr(weights), L.ptr(self.last_td), s)
         self.last_logits = (lr_all, lv_all, lp_all)
+        if tape is not None:
+            tape.update(dlr=dlr, dlv=dlv, dlp=dlp)
+        self.last_tape = tape
         # ---- backward
         # prediction k: heads -> res blocks -> d h_k (prediction part); independent of the dynamics
         # chain, so all K run first (side stream) and the chain adds them in
@@ -1107,7 +1122,11 @@ class Learner:
             if isinstance(gp, tuple):
                 gp, ev = gp
                 torch.cuda.current_stream(self.device).wait_event(ev)
+            if tape is not None:
+                tape["gps"][k] = gp.clone()
             L.call("mzba_axpy", self.dt, L.ptr(gh.t), L.ptr(gp), gh.t.numel(), s)  # d h_k += prediction part
+            if tape is not None:
+                tape["dh"][k] = gh.t.clone()
             gps[k] = None
             unroll[k] = None
         self._join(*crossing)

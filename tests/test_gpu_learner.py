@@ -239,7 +239,10 @@ def test_learner_bf16_tracks_f32():
     gradient cosine median >= 0.9 and min >= 0.5 (an f32 evaluation at parameters perturbed by
     1e-3 relative scores 0.98 / 0.89 here). The full-width nets are not compared this way: there
     the f32 gradient itself decorrelates under a 1e-4 relative parameter perturbation (cosine
-    0.34, tools/learner_bf16_study.py) — the k-step training loss is chaotic at that scale."""
+    0.34, tools/learner_bf16_study.py) — the k-step training loss is chaotic at that scale.
+    A cosine is blind to scale and to a few hundredths lost to a wiring error; the per-tensor check of the bf16
+    learner is tests/test_gpu_learner_tape.py (its own tape replayed in f64: forward layer by layer, the backward as
+    a linear map within twice the replay's rounding spread)."""
     from mzba.config import learner_model_cfg
     from mzba.learner import Learner
     from mzba.weights import init_state_dict
@@ -829,7 +832,9 @@ def test_learner_fused_bn_statistics_track_separate_passes():
     0.9998, median >= 0.94). What a wiring error (wrong consumer BN, mask or chunk) would break is how
     close each realisation is to the f32 parity path, so per seed (4 seeds) the fused run must be as
     close to f32 as the separate-pass run: median cosine within 0.02 (observed |diff| <= 0.019) and min
-    within 0.1 (observed >= -0.049); losses within 2e-3 relative (observed <= 1.5e-3)."""
+    within 0.1 (observed >= -0.049); losses within 2e-3 relative (observed <= 1.5e-3).
+    The wiring itself (consumer BN, mask, acc, segments) is checked per tensor, at the few-percent level, by
+    tests/test_gpu_learner_tape.py on the fused learner's own tape."""
     from mzba.config import learner_model_cfg
     from mzba.learner import Learner
     from mzba.weights import init_state_dict
