@@ -342,6 +342,38 @@ int mzba_replay_stream_gather(const mzba_sink* sink, int H, int W, int paddle_wi
                               uint64_t seed, uint32_t step, const uint32_t* step_dev, const mzba_replay_ring* ring,
                               int slot0, const float* dpow, int32_t* idx_out, hipStream_t stream);
 
+/* Episode statistics of a streamed sink (csrc/episode_stats.hip), accumulated on the device. A segment
+ * is closed if another start word follows it in the stage, the last one of an env iff done[b] || hlen[b] >= cap_len
+ * (stream_plan's rule). An episode is a closed segment with L >= 1 records; per env they are numbered in row order, and
+ * episode i is counted iff first_n == 0 || i < first_n. Every field below is over the counted episodes. The block
+ * accumulates: a call adds to what it finds, a zeroed block is the empty one (the extremes of a block with
+ * episodes == 0 are not read). */
+typedef struct mzba_episode_stats {
+  int64_t episodes, capped, rows;        /* counted episodes; those with L >= cap_len; sum of L */
+  double ret_sum, ret_sq;                /* sum of R and of R^2, R = the f32 sum of the episode's rewards added in row
+                                            order (the plan table's reward sum) */
+  float ret_min, ret_max;
+  int32_t len_min, len_max;
+  int64_t hist[32];                      /* bin clamp(floor((R - hist_lo) / hist_step), 0, 31), in double */
+  int64_t verr_rows;                     /* records of the episodes with L < cap_len (true terminals) */
+  double verr_sum, verr_abs, verr_sq;    /* of e_t = (double)values[t] - G_t over those records, G_t = r_t + gamma
+                                            G_{t+1} in double, 0 past the last record */
+  double value_sum;                      /* sum of values[t] over every record */
+  double entropy_sum;                    /* sum of -sum_a p_a ln p_a, p = counts / sum(counts), in double; 0 ln 0 = 0,
+                                            a row with sum(counts) <= 0 adds 0 */
+} mzba_episode_stats;                    /* 360 bytes */
+/* One thread per env walks its column, a second launch of one workgroup folds the envs' partial sums (ws, at least
+ * ws_bytes(B) bytes, 8-byte aligned) in a fixed order and adds them to the block: no floating-point atomics, the same
+ * bits on every run. No host synchronisation. ep_ret f32 [B][ep_n] / ep_len i32 [B][ep_n] (each may be NULL): R and L
+ * of the first ep_n counted episodes of each env, 0 in the unused entries. Reads the sink's start and mask everywhere,
+ * its reward, values and counts at the records only. -1: a NULL sink, sink->start, other read field, done, hlen, block
+ * or ws; cap_len < 1, first_n < 0, ep_n < 0, hist_step <= 0 or a workspace that is too small. */
+long long mzba_stream_episode_stats_ws_bytes(int B);
+int mzba_stream_episode_stats(const mzba_sink* sink, const uint8_t* done, const int32_t* hlen, int cap_len,
+                              int first_n, double gamma, double hist_lo, double hist_step, mzba_episode_stats* block,
+                              float* ep_ret, int32_t* ep_len, int ep_n, void* ws, long long ws_bytes,
+                              hipStream_t stream);
+
 /* ===================== prioritized replay (MuZero, Appendix G; csrc/replay_prio.hip)
  * q f32[cap], 16-byte aligned, in slot space: q[slot] = p^alpha for a live window, exactly 0 for a slot that
  * holds no window (the owner zeroes q when it empties the ring), so the sampler needs neither the ring's start
@@ -891,7 +923,7 @@ int mzba_replay_priority_update_g(float* q, const int32_t* slots, const float* t
                                   float eps, const mzba_guard_block* block, hipStream_t stream);
 
 /* sizeof of an ABI struct by its name (mzba_env_state, mzba_sink, mzba_replay_ring, mzba_tower_ext,
- * mzba_tree_step, mzba_gumbel), -1 for another name: a binding checks its mirror of each struct against it when it loads. */
+ * mzba_tree_step, mzba_gumbel, mzba_episode_stats), -1 for another name: a binding checks its mirror of each struct against it when it loads. */
 int mzba_struct_bytes(const char* name);
 
 #ifdef __cplusplus

@@ -666,6 +666,7 @@ int mzba_struct_bytes(const char* name) {
   MZ_STRUCT_BYTES(mzba_tower_ext);
   MZ_STRUCT_BYTES(mzba_tree_step);
   MZ_STRUCT_BYTES(mzba_gumbel);
+  MZ_STRUCT_BYTES(mzba_episode_stats);
 #undef MZ_STRUCT_BYTES
   return -1;
 }

@@ -1,6 +1,6 @@
 """mzba: MuZero on Breakout for the MI355X. The opt-in classes are reachable from the package by name and
 imported on first use, so `import mzba` itself stays free of torch and of the HIP library."""
-_OPT_IN = {"SinkArchive": "archive", "StagedWindows": "archive"}
+_OPT_IN = {"SinkArchive": "archive", "StagedWindows": "archive", "EpisodeStats": "stats", "Trainer": "train"}
 
 
 def __getattr__(name):

@@ -72,6 +72,9 @@ SIGNATURES = {
     "mzba_replay_stream_write": [P, I, I, I, I, P, I, I, I, P, I, P, P],
     # the sink archive's window gather (replay.hip)
     "mzba_replay_stream_gather": [P, I, I, I, I, P, I, P, P, I, U64, U32, P, P, I, P, P, P],
+    # episode statistics of a streamed sink (episode_stats.hip): the device block is an EpisodeStats
+    "mzba_stream_episode_stats_ws_bytes": [I],
+    "mzba_stream_episode_stats": [P, P, P, I, I, D, D, D, P, P, P, I, P, LL, P],
     # prioritized replay (replay_prio.hip)
     "mzba_replay_priority_init": [P, P, P, I, I, I, I, F, F, P],
     "mzba_replay_priority_update": [P, P, P, I, I, F, F, P],
@@ -215,16 +218,26 @@ class Gumbel(ctypes.Structure):
                 ("gumbel_scale", F)]
 
 
+class EpisodeStats(ctypes.Structure):
+    """include/mzba.h mzba_episode_stats (the device block mzba_stream_episode_stats accumulates into)."""
+    _fields_ = [("episodes", ctypes.c_int64), ("capped", ctypes.c_int64), ("rows", ctypes.c_int64),
+                ("ret_sum", D), ("ret_sq", D), ("ret_min", F), ("ret_max", F), ("len_min", ctypes.c_int32),
+                ("len_max", ctypes.c_int32), ("hist", ctypes.c_int64 * 32), ("verr_rows", ctypes.c_int64),
+                ("verr_sum", D), ("verr_abs", D), ("verr_sq", D), ("value_sum", D), ("entropy_sum", D)]
+
+
 # every struct of the ABI and its mirror here; lib() checks the sizes against mzba_struct_bytes
 STRUCTS = {"mzba_env_state": EnvState, "mzba_sink": Sink, "mzba_replay_ring": ReplayRing, "mzba_tower_ext": TowerExt,
            "mzba_tree_step": TreeStep}
 # the opt-in search mode's struct, checked the same way
 GUMBEL_STRUCTS = {"mzba_gumbel": Gumbel}
+# the episode statistics' device block, checked the same way
+STATS_STRUCTS = {"mzba_episode_stats": EpisodeStats}
 
 # entry points that return something other than a status code
 RESTYPES = {"mzba_tower_ws_bytes": LL, "mzba_tower_plan": I, "mzba_conv_lat_get_variant": I, "mzba_conv_wgrad_ws_bytes": LL,
             "mzba_linear_ws_bytes": LL, "mzba_learner_loss_ws_bytes": LL, "mzba_replay_sample_ws_bytes": LL,
-            "mzba_archive_sample_ws_bytes": LL,
+            "mzba_archive_sample_ws_bytes": LL, "mzba_stream_episode_stats_ws_bytes": LL,
             "mzba_grad_stats_ws_bytes": LL}
 
 
@@ -243,7 +256,7 @@ def lib():
             fn = getattr(L, name)
             fn.argtypes = argt
             fn.restype = RESTYPES.get(name, ctypes.c_int)
-        for name, cls in {**STRUCTS, **GUMBEL_STRUCTS}.items():
+        for name, cls in {**STRUCTS, **GUMBEL_STRUCTS, **STATS_STRUCTS}.items():
             if L.mzba_struct_bytes(name.encode()) != ctypes.sizeof(cls):
                 raise RuntimeError(f"mzba: {LIB_PATH} was built with another {name} than this binding's "
                                    f"({L.mzba_struct_bytes(name.encode())} bytes, {ctypes.sizeof(cls)} here)")

@@ -180,6 +180,40 @@ class SinkArchive:
         return self.append(loop.rec, stage.steps, env.done, env.hist_len, tail=tail,
                            search_id0=stage.last_search_id0)
 
+    # -- checkpoint (mzba.train.Trainer.save / load) --------------------------------------------------------
+    def state(self, sinks=True):
+        """What a resumed run needs, as host tensors and plain values: the seven sink tensors (sinks=False: None, the
+        resume then starts from an empty archive), `appended`, `search_id0`, `draw_step`, and `q` when prioritized. The
+        plan is not stored: `load_state` plans again."""
+        return {"rec": {k: v.cpu() for k, v in self.rec.items()} if sinks else None,
+                "q": self._q.cpu() if sinks and self.prioritized else None,
+                "appended": self.appended, "search_id0": list(self.search_id0), "draw_step": self.draw_step,
+                "shape": [self.slabs, self.steps, self.B, self.H * self.W], "prioritized": self.prioritized}
+
+    def load_state(self, st):
+        """Inverse of `state` into this archive's own tensors (their addresses stay, so captured gathers stay valid),
+        then the plan and its one host read. Without sink tensors the archive is emptied; `draw_step` is kept either
+        way, so no draw of the saved run is repeated."""
+        if list(st["shape"]) != [self.slabs, self.steps, self.B, self.H * self.W]:
+            raise ValueError(f"SinkArchive.load_state: saved shape {list(st['shape'])} is not this archive's")
+        if st["rec"] is not None and bool(st["prioritized"]) != self.prioritized:
+            raise ValueError("SinkArchive.load_state: the saved archive's prioritized flag is not this archive's")
+        if st["rec"] is None:
+            for v in self.rec.values():
+                v.zero_()
+            self.appended, self.search_id0 = 0, [None] * self.slabs
+            if self.prioritized:
+                self._q.zero_()
+        else:
+            for k, v in self.rec.items():
+                v.copy_(st["rec"][k])
+            self.appended, self.search_id0 = int(st["appended"]), list(st["search_id0"])
+            if self.prioritized:
+                self._q.copy_(st["q"])
+        self.draw_step = int(st["draw_step"])
+        self._plan()
+        self.segments, self.windows = self._totals.tolist()
+
     # -- windows on draw ----------------------------------------------------------------------------------
     def staged(self, capacity):
         """The archive's own staging area of `capacity` windows (one per capacity, kept)."""

@@ -33,15 +33,15 @@ def fresh_optimizer_state(mcfg, lr=None):
     return {"state": {}, "param_groups": [group]}
 
 
-def save_checkpoint(path, agent, replay=None, training_iteration=0, acting_step=0, iteration=0,
-                    optimizer_state=None, learner=None):
-    """train_torch.py:612-637. The optimizer state is, in order of preference: `optimizer_state`,
-    `learner.optimizer_state_dict()`, a fresh Adam state for the agent's parameters."""
+def checkpoint_dict(agent, replay=None, training_iteration=0, acting_step=0, iteration=0, optimizer_state=None,
+                    learner=None):
+    """The dict `save_checkpoint` writes (train_torch.py:612-637). The optimizer state is, in order of preference:
+    `optimizer_state`, `learner.optimizer_state_dict()`, a fresh Adam state for the agent's parameters."""
     sd = {k: (v.detach().clone() if torch.is_tensor(v) else torch.from_numpy(np.array(v, copy=True)))
           for k, v in agent.state_dict().items()}  # own copies; keeps 0-d shapes
     if optimizer_state is None:
         optimizer_state = learner.optimizer_state_dict() if learner is not None else fresh_optimizer_state(agent.cfg)
-    torch.save({
+    return {
         "model_state_dict": sd,
         "optimizer_state_dict": optimizer_state,
         "training_iteration": training_iteration,
@@ -49,7 +49,14 @@ def save_checkpoint(path, agent, replay=None, training_iteration=0, acting_step=
         "iteration": iteration,
         "replay_buffer": replay.to_reference_lists() if replay is not None else
         {k: ([] if k not in ("length", "max_length") else 0) for k in REPLAY_KEYS},
-    }, path)
+    }
+
+
+def save_checkpoint(path, agent, replay=None, training_iteration=0, acting_step=0, iteration=0,
+                    optimizer_state=None, learner=None):
+    """train_torch.py:612-637: `checkpoint_dict` of the same arguments, written to `path`."""
+    torch.save(checkpoint_dict(agent, replay, training_iteration, acting_step, iteration, optimizer_state, learner),
+               path)
 
 
 def load_checkpoint(path, agent=None, replay=None, learner=None):

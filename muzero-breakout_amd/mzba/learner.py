@@ -318,6 +318,42 @@ class Learner:
             if d.get("param_groups") and (g is None or (g.lr_schedule is None and g.lr_dev is None)):
                 self.lr = float(d["param_groups"][0]["lr"])
 
+    # -- raw state (mzba.train.Trainer.save / load: a resume that continues bit for bit) -----------------------
+    def state(self):
+        """The learner as it stands, in its own layouts, as host tensors and plain values: the flat master weights
+        and Adam moments, every running mean and variance, the BN batch counters, the step counters (minibatches, and
+        prioritized steps: the sampler's Philox step) and the guard's device block."""
+        return {"P": self.P.cpu(), "M1": self.M1.cpu(), "M2": self.M2.cpu(),
+                "run_mean": {k: self.run[k][0].cpu() for k in self.bn_keys},
+                "run_var": {k: self.run[k][1].cpu() for k in self.bn_keys},
+                "nbt": {k: int(self.nbt[k]) for k in self.bn_keys},
+                "step_count": self.step_count, "per_step": self.per_step,
+                "guard_block": self.guard_block.cpu() if self.guard is not None else None}
+
+    def load_state(self, st):
+        """Inverse of `state`, written into this learner's own tensors: their addresses stay, so a captured graph
+        and an agent's refresh table stay valid."""
+        if st["P"].numel() != self.n_flat or sorted(st["nbt"]) != sorted(self.bn_keys):
+            raise ValueError("Learner.load_state: the saved learner has another configuration")
+        if (st["guard_block"] is None) != (self.guard is None):
+            raise ValueError("Learner.load_state: the saved learner and this one differ in having a step guard")
+        with torch.no_grad():
+            self.P.copy_(st["P"])
+            self.M1.copy_(st["M1"])
+            self.M2.copy_(st["M2"])
+            for k in self.bn_keys:
+                self.run[k][0].copy_(st["run_mean"][k])
+                self.run[k][1].copy_(st["run_var"][k])
+                self.nbt[k] = int(st["nbt"][k])
+            self.step_count, self.per_step = int(st["step_count"]), int(st["per_step"])
+            if self.guard is not None:
+                self.guard_block.copy_(st["guard_block"])
+
+    def captured_for(self, ring, B, prioritized=False, seed=0):
+        """Whether train_minibatch / prioritized_step on (ring, B) replays a graph captured by `capture`."""
+        return (self._graph is not None and self._g_prio == bool(prioritized) and ring is self._g_ring and
+                B == self._g_slots.numel() and (not prioritized or int(seed) == self._g_seed))
+
     # -- the step guard (csrc/guard.hip) ----------------------------------------------------------
     def _guard_init(self):
         """The guard's device state: the stats block, the reduction's scratch and the segment bounds (one per net:

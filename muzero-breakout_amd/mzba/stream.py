@@ -112,6 +112,18 @@ class StreamingStage:
     def set_noise_weight(self, w):
         self.loop.search.noise_weight = w  # copied to the device before the next step
 
+    def state(self):
+        """The host counters a resumed run continues from (between stages nothing else is carried: every stage resets
+        all envs under its own key): the next stage's ep_base, the loop's search id and step index, and the search id
+        of the last stage's row 0."""
+        return {"ep_base": self.ep_base, "search_id": self.loop.search_id, "step_index": self.loop.step_index,
+                "last_search_id0": self.last_search_id0}
+
+    def load_state(self, st):
+        self.ep_base = int(st["ep_base"])
+        self.loop.search_id, self.loop.step_index = int(st["search_id"]), int(st["step_index"])
+        self.last_search_id0 = st["last_search_id0"]
+
     def run(self, replay_buffer=None, trajectories=False, tail="drop"):
         """One stage: reset under ep_base, exactly `steps` steps with no host synchronisation between them, then
         the ingest into `replay_buffer` (its counts: replay_buffer.last_stream) and/or the segments' host
